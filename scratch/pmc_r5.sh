@@ -4,8 +4,8 @@
 #   gpurun -- bash scratch/pmc_r5.sh ; python scratch/collect_r5.py
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_r5; rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- python3 bench.py --steps 50 --warmup 5 --repeats 20 --no-cpu-baseline --no-train-step --no-eval-sweep > $O/bench_under_rocprof.json 2> $O/trace.log
+python3 bench.py --full --repeats 50 > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- python3 bench.py --full --steps 50 --warmup 5 --repeats 20 --no-cpu-baseline --no-train-step --no-eval-sweep > $O/bench_under_rocprof.json 2> $O/trace.log
 for mode in warm cold; do
   rocprofv3 --pmc FETCH_SIZE -d $O/fetch_$mode --output-format csv -- python3 scratch/prof_step_r5.py 24 $mode > /dev/null 2>&1
   rocprofv3 --pmc WRITE_SIZE -d $O/write_$mode --output-format csv -- python3 scratch/prof_step_r5.py 24 $mode > /dev/null 2>&1

@@ -59,7 +59,7 @@ def test_bench_distributed_branch_with_one_rank(tmp_path):
     RCCL's own rank count, per-rank step times, the DDP train step with its RCCL time and overlap fields, the loader-fed
     epoch in distributed mode, the sharded sweep with the merge inside the clock."""
     from tests import _gpu_children
-    argv = ["--gpus", "1", "--steps", "5", "--warmup", "5", "--repeats", "3", "--train-steps", "2", "--train-warmup", "2", "--e2e-steps", "2",
+    argv = ["--gpus", "1", "--full", "--steps", "5", "--warmup", "5", "--repeats", "3", "--train-steps", "2", "--train-warmup", "2", "--e2e-steps", "2",
             "--e2e-warmup", "1", "--sweep-images", "2", "--no-cpu-baseline", "--cold-sets", "0", "--graph-steps", "4"]
     d = _run_child(_gpu_children.bench_forced_dist, tmp_path, argv, timeout=2400)
     assert d["n_gpus"] == 1 and d["world_size_seen_by_rccl"] == 1 and d["rank_devices"] == [0]
