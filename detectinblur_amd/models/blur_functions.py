@@ -30,7 +30,10 @@ def _post_ops(output, add_noise, noise_level, add_block, add_jpeg_artifact, jpeg
         if np.random.uniform(0, 1) > 0.5:
             block_scale = np.random.uniform(0.6, 1)
     if noise_var is not None or block_scale is not None:
-        if FUSE_POST_OPS and output.is_cuda and output.dtype in blur_ops._DT and output.dim() in (2, 3):
+        # a 2-D image (one channel, squeezed by manual_blur) with a block draw takes the stock ops: the reference's
+        # `interpolate(output.unsqueeze(0), scale_factor=(s, s))` raises on it (3-D input, two scale factors), and so must we
+        fused_shape = output.dim() == 3 or (output.dim() == 2 and block_scale is None)
+        if FUSE_POST_OPS and output.is_cuda and output.dtype in blur_ops._DT and fused_shape:
             output = blur_ops.post_ops(output, noise_var, block_scale)
         else:
             if noise_var is not None:

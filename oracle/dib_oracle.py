@@ -580,3 +580,240 @@ def cpu_fft_blur(image_u8, psf):
     blurred = _minmax01(blurred)
     blurred = blurred[pr:blurred.shape[0] - pr, pr:blurred.shape[1] - pr, :]
     return (blurred * 255).astype(np.uint8)
+
+
+# --------------------------------------------------------------------------------------
+# A16 post-blur corruption chain: noise + clamp, block artefacts, JPEG round trip
+#     (reference models/blur_functions.py:72-87, transforms.py:467-493, models/jpeg/*)
+# --------------------------------------------------------------------------------------
+# Float64 references for the two post-op kernels (csrc/dib_postops.hip, csrc/dib_jpeg.hip).  Each returns the expected
+# result together with what float64 cannot decide about the kernel's fp32 arithmetic: a per-pixel error bound (JPEG) or
+# the set of elements whose fp16 rounding is not determined (noise).
+
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(counters, key):
+    """Philox-4x32-10 (Salmon et al., SC'11; the Random123 definition) on an array of counters [..., 4] (uint32) under
+    the key (k0, k1): ten rounds, the key bumped by the Weyl constants after each.  dib_postops.hip philox_round."""
+    c = np.asarray(counters, dtype=np.uint64)
+    c0, c1, c2, c3 = (c[..., i] & _U32 for i in range(4))
+    k0, k1 = np.uint64(int(key[0]) & 0xFFFFFFFF), np.uint64(int(key[1]) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0 = c0 * np.uint64(0xD2511F53)          # < 2^64: exact in uint64
+        p1 = c2 * np.uint64(0xCD9E8D57)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _U32
+        k0 = (k0 + np.uint64(0x9E3779B9)) & _U32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & _U32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def post_ops_key(torch_seed):
+    """The noise field's key as blur_ops.post_ops draws it: one int64 from torch's host generator after
+    torch.manual_seed(torch_seed).  Returns (key0, key1) = (low, high) 32-bit words."""
+    import torch
+    torch.manual_seed(torch_seed)
+    s = int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF
+    return s & 0xFFFFFFFF, s >> 32
+
+
+def normal64(index, key):
+    """The kernel's normal at each element index (dib_postops.hip normal_at): Philox on counter (index, 0, 0, 0), the two
+    uniforms formed in float32 exactly as the kernel forms them (`(float)(w >> 8) + 0.5f` rounds above 2^23), the angle
+    2 pi u2 rounded to float32 as the kernel's product is; then Box-Muller in float64.  The kernel's __logf / __cosf /
+    sqrtf and its two fp32 products differ from this by at most eps_n (measured: tests/test_postops_reference.py)."""
+    index = np.asarray(index, dtype=np.uint64)
+    ctr = np.zeros(index.shape + (4,), dtype=np.uint64)
+    ctr[..., 0] = index & _U32
+    ctr[..., 1] = index >> np.uint64(32)
+    w = philox4x32_10(ctr, key)
+    inv = np.float32(1.0 / 16777216.0)
+    u1 = ((w[..., 0] >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * inv
+    u2 = ((w[..., 1] >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * inv
+    ang = np.float32(6.28318530717958647692) * u2
+    return np.sqrt(-2.0 * np.log(u1.astype(np.float64))) * np.cos(ang.astype(np.float64))
+
+
+def _half_boundary_distance(n):
+    """Distance of each float64 `n` from the nearest fp16 round-to-nearest boundary (midpoint of two adjacent halves)."""
+    h = n.astype(np.float16)
+    up = np.nextafter(h, np.float16(np.inf)).astype(np.float64)
+    dn = np.nextafter(h, np.float16(-np.inf)).astype(np.float64)
+    hd = h.astype(np.float64)
+    return np.minimum(np.abs(n - (hd + up) / 2), np.abs(n - (hd + dn) / 2))
+
+
+def block_source_map(H, W, block_scale):
+    """Source row / column of every output row / column under the block arm: interpolate(scale_factor=s) then
+    interpolate(size=(H, W)), both 'nearest' (blur_functions.py:76-81), composed as dib_postops.hip does it in fp32 --
+    ATen upsample_nearest2d's src = min(floor(dst * scale), in - 1) with scale = float(1 / s) for the first call and
+    float(in) / out for the second; the first call's size = floor(double(in) * s)."""
+    if not block_scale:
+        return np.arange(H), np.arange(W)
+    f32 = np.float32
+    hs, ws = int(math.floor(H * block_scale)), int(math.floor(W * block_scale))
+    down = f32(1.0 / block_scale)
+    up_h, up_w = f32(hs) / f32(H), f32(ws) / f32(W)
+
+    def comp(n, m, up):
+        mid = np.minimum(np.floor(np.arange(n, dtype=np.float32) * up).astype(np.int64), m - 1)
+        return np.minimum(np.floor(mid.astype(np.float32) * down).astype(np.int64), n - 1)
+    return comp(H, hs, up_h), comp(W, ws, up_w)
+
+
+def post_ops64(img, noise_var, block_scale, seed, eps_n):
+    """Expected output of dib_post_ops on a C x H x W (or H x W) float16 / float32 image (blur_functions.py:72-81 as
+    the kernel computes it), and the mask of output elements whose value is not determined by float64.
+
+    seed: the torch.manual_seed value in force when blur_ops.post_ops draws the key (post_ops_key).
+    Noise: element (c, y, x) reads source (c, sy, sx) through the composed block maps and adds the normal at counter
+    c*H*W + sy*W + sx.  float16: n16 = half(n), prod = half(float(n16) * float(std)), out = half(v + prod), clamp --
+    each step restated exactly in numpy's IEEE float32 / float16; only n comes from the kernel's approximate __logf /
+    __cosf, so an element is not determined when n lies within eps_n of an fp16 rounding boundary AND the two
+    candidate n16 on either side give different outputs (given n16, the rest -- clamp included, which acts on an fp16
+    value -- is exact).  float32: out = v + f32(n * std), clamp; the
+    expected value uses float64 n and the mask is empty -- compare within eps_n * std plus one ulp."""
+    a = np.asarray(img)
+    if a.dtype not in (np.float16, np.float32):
+        raise TypeError("post_ops64: float16 / float32 image")
+    x = a[None] if a.ndim == 2 else a
+    C, H, W = x.shape
+    undet = np.zeros(x.shape, dtype=bool)
+    out = x.copy()
+    if noise_var:
+        std = np.float32(math.sqrt(noise_var))
+        key = post_ops_key(seed)
+        n = normal64(np.arange(C * H * W, dtype=np.uint64), key).reshape(C, H, W)
+        if x.dtype == np.float16:
+            def half_chain(n16):
+                prod = (n16.astype(np.float32) * std).astype(np.float16)
+                o = (x.astype(np.float32) + prod.astype(np.float32)).astype(np.float16)
+                return np.minimum(np.maximum(o, np.float16(0)), np.float16(1))
+            out = half_chain(n.astype(np.float16))
+            # the kernel's n lies in [n - eps_n, n + eps_n]: eps_n << one fp16 ulp, so at most one rounding boundary is
+            # in reach and half(n - eps_n), half(n + eps_n) are the only candidates for its n16
+            near = _half_boundary_distance(n) <= eps_n
+            undet = near & (half_chain((n - eps_n).astype(np.float16)).view(np.uint16) != half_chain((n + eps_n).astype(np.float16)).view(np.uint16))
+        else:
+            out = x + (n.astype(np.float32) * std)
+            out = np.minimum(np.maximum(out, np.float32(0)), np.float32(1))
+    sy, sx = block_source_map(H, W, block_scale)
+    out, undet = out[:, sy][:, :, sx], undet[:, sy][:, :, sx]
+    if a.ndim == 2:
+        out, undet = out[0], undet[0]
+    return out, undet
+
+
+# JPEG round trip ------------------------------------------------------------------------
+# Standard tables as the reference holds them: models/jpeg/utils.py:7-21 (transposed: indexed [u][v]).
+JPEG_LUMA = np.array([[16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56],
+                      [14, 17, 22, 29, 51, 87, 80, 62], [18, 22, 37, 56, 68, 109, 103, 77], [24, 35, 55, 64, 81, 104, 113, 92],
+                      [49, 64, 78, 87, 103, 121, 120, 101], [72, 92, 95, 98, 112, 100, 103, 99]], dtype=np.float32).T
+JPEG_CHROMA = np.full((8, 8), 99, dtype=np.float32)
+JPEG_CHROMA[:4, :4] = np.array([[17, 18, 24, 47], [18, 21, 26, 66], [24, 26, 56, 99], [47, 66, 99, 99]], dtype=np.float32).T
+
+
+def jpeg_quality_factor(quality):
+    """models/jpeg/utils.py:34-45."""
+    q = 5000.0 / quality if quality < 50 else 200.0 - quality * 2
+    return q / 100.0 if quality < 50 else (q + 0.01) / 100.0
+
+
+# The colour matrices are the reference's fp32 buffers (compression.py:20-22, decompression.py:102-115): every
+# implementation multiplies by these fp32 values, so the float64 chain starts from them, exactly.
+_f64 = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)   # noqa: E731
+_TO_YCC = _f64([[0.299, 0.587, 0.114], [-0.168736, -0.331264, 0.5], [0.5, -0.418688, -0.081312]])
+_TO_RGB = _f64([[1.0, 0.0, 1.402], [1.0, -0.344136, -0.714136], [1.0, 1.772, 0.0]])
+_COS8 = np.cos((2 * np.arange(8)[:, None] + 1) * np.arange(8)[None, :] * np.pi / 16)     # [a, u]
+_ALPHA = np.array([1 / np.sqrt(2)] + [1.0] * 7)
+_AA4 = np.outer(_ALPHA, _ALPHA) / 4
+_U = 2.0 ** -24                                                   # fp32 unit roundoff
+
+
+def _gamma(n):
+    return n * _U / (1 - n * _U)
+
+
+def _blocks(p):        # [h, w] -> [h/8, w/8, 8, 8]
+    return p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).transpose(0, 2, 1, 3)
+
+
+def _planes(b):
+    return b.transpose(0, 2, 1, 3).reshape(b.shape[0] * 8, b.shape[1] * 8)
+
+
+def _code_decode(plane, q):
+    """One plane (pixel values - 128) through DCT, quantise, dequantise, inverse DCT.  Returns the decoded plane (+128),
+    the per-pixel bound of one quantisation step of every ambiguous coefficient of its block, the per-pixel fp32 error
+    of the inverse transform, and the per-block ambiguity flag.
+
+    Ambiguity threshold delta (per block, per coefficient), from the fp32 arithmetic of every implementation:
+      inputs: each Y / Cb / Cr value is x*255 and a 3-term dot with |row| <= 1 plus a shift (<= 383 in magnitude), the
+        chroma 2x2 mean and the -128 add two more steps: <= 10 roundings of values <= 383, e_in = 10 u 383;
+      the coefficient c = alpha_u alpha_v / 4 sum_ab blk cos cos: 64 products summed in ANY order (the kernel's nested
+        8 x 8, a GEMM's blocked order, the CPU tensordot) err <= gamma_64 S with S = sum |blk|; the basis (cosf or the
+        fp32 table) and the products before the sum add <= 10 u S; the input error adds <= 64 e_in (|cos cos| <= 1);
+        the alpha / 4 scale and the division by q one rounding each of |c| and |c / q|.
+      delta_uv = alpha_u alpha_v / 4 (gamma_64 S + 10 u S + 64 e_in) / q_uv + 3 u |c / q_uv|.
+    A coefficient with |frac(c / q) - 0.5| < delta may round either way and is ambiguous: one step q_uv either way,
+    which the inverse transform carries to pixel (a, b) as alpha_u alpha_v / 4 q_uv |cos_au cos_bv|.
+    With no ambiguous coefficient the integers are the same, and the decoded pixel differs by the fp32 error of the
+    inverse transform alone: a 64-term sum of |alpha deq cos cos| / 4 (T), any order, plus 10 u T for the basis and
+    the dequantising products, and the +128."""
+    b = _blocks(plane)
+    c = _AA4 * np.einsum("au,hwab,bv->hwuv", _COS8, b, _COS8)
+    ratio = c / q
+    S = np.abs(b).sum(axis=(2, 3))[..., None, None]
+    e_in = 10 * _U * 383.0
+    delta = _AA4 * ((_gamma(64) + 10 * _U) * S + 64 * e_in) / q + 3 * _U * np.abs(ratio)
+    amb = np.abs(ratio - np.floor(ratio) - 0.5) < delta
+    deq = np.rint(ratio) * q
+    dec = np.einsum("au,hwuv,bv->hwab", _COS8, _AA4 * deq, _COS8) + 128
+    flip = np.einsum("au,hwuv,bv->hwab", np.abs(_COS8), np.where(amb, _AA4 * q, 0.0), np.abs(_COS8))
+    T = (np.abs(_AA4 * deq)).sum(axis=(2, 3))[..., None, None]
+    err = ((_gamma(64) + 10 * _U) * T + 2 * _U * 1152.0) * np.ones_like(dec)
+    return _planes(dec), _planes(flip), _planes(err), amb.any(axis=(2, 3))
+
+
+def jpeg_roundtrip64(img, quality, pad=True):
+    """transforms.add_jpeg_artifact_to_image (transforms.py:467-493) around DiffJPEG (models/jpeg/DiffJPEG.py:
+    compression.py + decompression.py, rounding = torch.round) in float64 from the input's exact values, on one
+    3 x H x W image in [0, 1].  Returns (expected, bound, exact):
+      expected  3 x H x W float64 -- the round trip's value before the final fp16 cast;
+      bound     3 x H x W float64 -- |fp16 result - expected| allowed at each pixel: 1/2 fp16 ulp + the fp32 error of the
+                chain with the same quantised integers, + one quantisation step carried through the inverse DCT and the
+                colour matrix for every ambiguous coefficient of the blocks the pixel reads (see _code_decode);
+      exact     H x W bool -- the pixel's luma block and chroma blocks have no ambiguous coefficient.
+    pad=False: DiffJPEG alone on an image whose sides are multiples of 16 (no reflect pad / crop)."""
+    x = np.asarray(img).astype(np.float64)
+    _, H, W = x.shape
+    wp, hp = (16 - W % 16, 16 - H % 16) if pad else (0, 0)     # transforms.py:471-477: a full 16 when already a multiple
+    left, top = wp // 2, hp // 2
+    xp = np.pad(x, ((0, 0), (top, hp - top), (left, wp - left)), mode="reflect")
+    ycc = np.einsum("ij,jhw->ihw", _TO_YCC, xp * 255) + np.array([0.0, 128.0, 128.0])[:, None, None]
+    Hp, Wp = ycc.shape[1:]
+    pooled = ycc[1:].reshape(2, Hp // 2, 2, Wp // 2, 2).mean(axis=(2, 4))                  # avg_pool2d(2, 2)
+    fac = np.float32(jpeg_quality_factor(quality))
+    qy = (JPEG_LUMA * fac).astype(np.float64)
+    qc = (JPEG_CHROMA * fac).astype(np.float64)
+    y, fy, ey, ay = _code_decode(ycc[0] - 128, qy)
+    chans, flips, errs, ambs = [y], [fy], [ey], [np.kron(ay, np.ones((8, 8), dtype=bool))]
+    for k in (0, 1):
+        d, f, e, a = _code_decode(pooled[k] - 128, qc)
+        up = lambda p: p.repeat(2, axis=0).repeat(2, axis=1)      # noqa: E731
+        chans.append(up(d)); flips.append(up(f)); errs.append(up(e))
+        ambs.append(np.kron(a, np.ones((16, 16), dtype=bool)))
+    ycc_dec = np.stack(chans) - np.array([0.0, 128.0, 128.0])[:, None, None]
+    rgb = np.einsum("ij,jhw->ihw", _TO_RGB, ycc_dec)
+    A = np.abs(_TO_RGB)
+    flip = np.einsum("ij,jhw->ihw", A, np.stack(flips))
+    # the decoded planes' fp32 errors through the colour matrix, + 4 roundings of values <= 1152 (-128, products, sums),
+    # the clamp is 1-Lipschitz, / 255 one more rounding
+    err = np.einsum("ij,jhw->ihw", A, np.stack(errs)) + 4 * _U * 1152.0
+    out = np.clip(rgb, 0, 255) / 255
+    crop = (slice(None), slice(top, top + H), slice(left, left + W))
+    out, flip, err = out[crop], flip[crop] / 255, err[crop] / 255 + _U
+    exact = ~(ambs[0] | ambs[1] | ambs[2])[top:top + H, left:left + W]
+    hi = np.abs(out) + flip + err
+    half_ulp = np.spacing(hi.astype(np.float16)).astype(np.float64) / 2       # the final cast to fp16
+    return out, flip + err + half_ulp, exact

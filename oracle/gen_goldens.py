@@ -311,6 +311,26 @@ def gen_postops(ns, store):
         store["rng_after_%d" % seed] = np.array([np.random.uniform()])      # the draw order leaves numpy's stream here
 
 
+POSTOP_CHAIN_SEEDS = (0, 1, 2, 9)      # (block, jpeg) coins: (1, 1), (1, 0), (0, 1), (1, 0)
+
+
+def gen_postops_chain(ns, store):
+    """The whole post-blur chain of the reference's manual_blur (models/blur_functions.py:72-87: noise, block, JPEG via
+    transforms.add_jpeg_artifact_to_image around models/jpeg/DiffJPEG) on the CPU behind an identity PSF, seeded per
+    case; the seeds cover both arms of the JPEG coin (> 0.35) and of the block coin (> 0.5)."""
+    import importlib
+    J = importlib.import_module("models.jpeg.DiffJPEG")
+    x, delta = postop_input()
+    m = J.DiffJPEG(height=100, width=100, differentiable=False, quality=10)
+    for seed in POSTOP_CHAIN_SEEDS:
+        np.random.seed(seed); torch.manual_seed(seed)
+        with torch.no_grad():
+            out = ns.blur_functions.manual_blur(x.clone(), delta, add_noise=True, noise_level=0.004, add_block=True,
+                                                add_jpeg_artifact=True, jpeg_compressor=m)
+        store["chain_%d" % seed] = out.numpy()
+        store["chain_rng_after_%d" % seed] = np.array([np.random.uniform()])
+
+
 def jpeg_input():
     g = torch.Generator().manual_seed(2024)
     x = torch.rand(2, 3, 32, 48, generator=g)
@@ -462,6 +482,12 @@ def main():
         np.savez_compressed(os.path.join(OUT, "postops.npz"), **store)
         print("postops", len(store), "arrays; block cases changed:", [int(not np.array_equal(store["block_%d" % k], postop_input()[0].numpy())) for k in POSTOP_SEEDS])
         return
+    if "--only-postops-chain" in sys.argv:
+        store = {}
+        gen_postops_chain(ns, store)
+        np.savez_compressed(os.path.join(OUT, "postops_chain.npz"), **store)
+        print("postops_chain", {k: (v.shape, v.dtype.name) for k, v in store.items()})
+        return
     if "--only-warper" in sys.argv:
         store = {}
         gen_warper(ns, store)
@@ -480,7 +506,7 @@ def main():
     gen_psf_store(ns, meta)
     for name, fn in (("traj", gen_trajectories), ("psf", gen_psfs), ("boxes", gen_boxes),
                      ("norm", gen_norm), ("fft", gen_fft), ("warper", gen_warper), ("jpeg", gen_jpeg), ("coco", gen_coco_eval),
-                     ("net_transforms", gen_net_transforms), ("postops", gen_postops)):
+                     ("net_transforms", gen_net_transforms), ("postops", gen_postops), ("postops_chain", gen_postops_chain)):
         store = {}
         fn(ns, store)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
