@@ -39,7 +39,8 @@ def build_parser():
     # outside the built path: accepted, refused when set
     p.add_argument("--blurred_dataset", action="store_true", help="(not built) real-blur datasets")
     p.add_argument("--expand_synth_boxes", action="store_true", help="(not built) real-blur datasets")
-    p.add_argument("--mode_one_norm", action="store_true", help="(not built) batch-norm remedy")
+    p.add_argument("--mode_one_norm", action="store_true", help="Test-time batch-norm: every layer mixes the image's statistics "
+                   "into its running ones (single model only, as in the reference)")
     return p
 
 
@@ -69,9 +70,14 @@ def main(args):
         # reference scores sharp images against the sweep's labels without saying so
         print("Warning: neither --gpu_blur nor --cpu_blur: the sweep will score UNBLURRED images.")
 
-    def detector(path=None):
+    def detector(path=None, mode_one=False):
         m = _load(fasterrcnn_resnet50_fpn(num_classes=91, pretrained=args.pretrained, pretrained_backbone=False,
                                           warp_internally=args.warp_in_model, **detector_size_kwargs(args)), path).to(device)
+        if mode_one:                                                    # reference evaluate.py:234-237, before DDP wrapping
+            from .models.batchnorm import BatchNorm2d
+            m = utils.convert_to_custom_batch_norm(m, batch_norm_to_use=BatchNorm2d)
+            m = utils.set_batch_norm_N(m, 16)
+            m = utils.set_batch_norm_mode1(m, True)
         if not args.distributed:
             return m
         return torch.nn.parallel.DistributedDataParallel(m, device_ids=[args.gpu] if device.type == "cuda" else None,
@@ -79,6 +85,8 @@ def main(args):
 
     ensemble, estimator, model = None, None, None
     if args.use_ensemble:                                               # reference evaluate.py:159-205
+        if getattr(args, "mode_one_norm", False):
+            print("--mode_one_norm is ignored with --use_ensemble (as in the reference: the remedy applies to a single model)")
         # the README passes the four paths as ONE quoted string (evaluate.py:161 splits element 0)
         paths = [q for p_ in (args.ensemble_model_paths or []) for q in p_.split()] or [None] * 4
         ensemble = [detector(p_) for p_ in paths]
@@ -87,7 +95,7 @@ def main(args):
             estimator.fc = nn.Linear(512, 4 if args.LEHE else 16)
             estimator = _load(estimator, args.blur_estimator_path).to(device)
     else:
-        model = detector(args.resume or args.model_path)
+        model = detector(args.resume or args.model_path, mode_one=getattr(args, "mode_one_norm", False))
 
     def loader_for(tf):
         ds, _ = get_coco(args.data_path, "val", tf, synthetic=synthetic, with_masks=getattr(args, "with_masks", False))

@@ -16,6 +16,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .batchnorm import BatchNorm2d
+
 
 class FrozenBatchNorm2d(nn.Module):
     """BatchNorm with fixed statistics and affine parameters: y = x * scale + shift."""
@@ -581,9 +583,16 @@ def _wide_out(x, conv):
             and 16384 < x.shape[0] * x.shape[2] * x.shape[3] <= 65536)
 
 
+# Test-time batch-norm statistics (`--mode_one_norm`, models/batchnorm.py): the convolution runs unfolded (the statistics are the
+# input's), then ONE call does statistics + normalisation + residual + ReLU in place on its output (dib_bn_mode_one_nhwc: three
+# launches, ~3 passes).  Set to False to run the reference's torch expression instead (A/B runs).
+FUSE_TEST_TIME_BN = True
+
+
 def conv_bn(x, conv, bn, relu=False, residual=None):
     """conv -> frozen batch-norm (-> + residual) (-> ReLU).  With FOLD_FROZEN_BN the norm's scale goes
-    into the weights and its shift into the fused epilogue."""
+    into the weights and its shift into the fused epilogue; a test-time (mode one) batch-norm runs behind the unfolded
+    convolution as one fused call."""
     if FOLD_FROZEN_BN and isinstance(bn, FrozenBatchNorm2d) and conv.bias is None:
         if torch.is_grad_enabled() and conv.weight.requires_grad:
             weight, shift = _train_fold(conv, bn)
@@ -591,6 +600,9 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
             weight, shift = _folded(conv, bn)
         y = _WideOut1x1.apply(x, weight) if _wide_out(x, conv) else conv1x1(x, weight, None, conv)
         return bias_act(y, shift, residual, relu)
+    if isinstance(bn, BatchNorm2d) and bn.mode_one:
+        # the same convolution detours as the folded path (same MIOpen / hipBLASLt shapes), on the unfolded weight
+        return bn.forward_fused_(conv1x1(x, conv.weight, conv.bias, conv), residual, relu)
     y = bn(conv(x))
     if residual is not None:
         y = y + residual

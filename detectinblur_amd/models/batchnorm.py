@@ -1,0 +1,124 @@
+"""`BatchNorm2d` with the reference's test-time "mode one" (reference models/batchnorm.py:159-184; `evaluate.py
+--mode_one_norm`): every batch-norm layer normalises with its running statistics mixed with the statistics of the batch it
+sees, whatever `self.training` says,
+
+    mean = f * running_mean + g * mean_b,   var = f * running_var + g * var_b,   f = n / (n + 1),  g = 1 / (n + 1)
+
+with n = num_batches_tracked and var_b the biased variance over N x H x W -- zero padding of the batched images included.
+Two ways to the same values:
+
+  * HIP (include/dib.h: dib_bn_mode_one_nhwc): a CUDA fp32 channels-last tensor with C % 4 == 0 and no autograd graph to
+    build -- partial Welford statistics, the mix and the fused scale / shift (+ residual) (+ ReLU) pass, three launches;
+  * torch: everything else (CPU, planar tensors, gradients), a line-for-line restatement of the reference's forward, bit for
+    bit its values (tests/test_mode_one_norm.py).
+
+With `mode_one` off the module is `torch.nn.BatchNorm2d`.  The reference's `acclimation_mode` is not offered: no driver
+reaches it.  `last_path` records which of the two ran last ("hip" / "torch"), for tests and A/B runs; the switch for those
+is backbone.FUSE_TEST_TIME_BN.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+
+class BatchNorm2d(nn.BatchNorm2d):
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None):
+        super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
+        self.mode_one = False
+        self.last_path = None
+
+    # ---- which path ------------------------------------------------------------------------------------------------------------
+    def _hip_ok(self, x, residual=None):
+        from . import backbone
+        if not (backbone.FUSE_TEST_TIME_BN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0
+                and x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15)):
+            return False
+        if self.running_mean is None or self.running_var is None or (self.training and not self.track_running_stats):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or (self.weight is not None and self.weight.requires_grad)
+                                        or (self.bias is not None and self.bias.requires_grad)
+                                        or (residual is not None and residual.requires_grad)):
+            return False
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            return False                # the reference bumps num_batches_tracked first: the torch path does that
+        dev = x.device
+        for t in (self.weight, self.bias, self.running_mean, self.running_var):
+            if t is not None and not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                return False
+        nbt = self.num_batches_tracked
+        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.numel() == 1 and (nbt.device == dev or nbt.device.type == "cpu")):
+            return False
+        return residual is None or (residual.shape == x.shape and residual.dtype == torch.float32 and residual.device == dev
+                                    and residual.is_contiguous(memory_format=torch.channels_last) and not (residual.data_ptr() & 15))
+
+    # ---- the two paths ---------------------------------------------------------------------------------------------------------
+    def _mode_one_hip_(self, x, residual=None, relu=False, stats=None):
+        """x = act(bn(x) (+ residual)) in place (dib_bn_mode_one_nhwc).  `stats`: a [2, C] fp32 CUDA tensor that receives the mixed
+        mean and variance."""
+        from .. import _lib
+        N, C, H, W = x.shape
+        npix = N * H * W
+        l = _lib.lib()
+        nbytes = l.dib_bn_mode_one_workspace_bytes(npix, C)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=x.device)      # the caching allocator (a graph's pool under capture)
+        nbt = self.num_batches_tracked
+        if nbt is None:
+            nb_dev, nb_host = None, 0
+        elif nbt.is_cuda:
+            nb_dev, nb_host = nbt.data_ptr(), 0          # read on the device: no host synchronisation
+        else:
+            nb_dev, nb_host = None, int(nbt)             # a CPU tensor: read here (a captured graph keeps this value)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        _lib.check(l.dib_bn_mode_one_nhwc(x.data_ptr(), ptr(residual), npix, C, ptr(self.weight), ptr(self.bias),
+                                          self.running_mean.data_ptr(), self.running_var.data_ptr(), nb_dev, nb_host, float(self.eps),
+                                          int(bool(relu)), ws.data_ptr(), ws.numel() * 4, ptr(stats), _lib.stream_of(x)))
+        self.last_path = "hip"
+        return x
+
+    def _mode_one_torch(self, input):
+        """reference models/batchnorm.py:97-184 for mode_one (acclimation off), statement for statement."""
+        if self.momentum is None:
+            exponential_average_factor = 0.0
+        else:
+            exponential_average_factor = self.momentum
+        if self.training and self.track_running_stats:
+            if self.num_batches_tracked is not None:
+                self.num_batches_tracked = self.num_batches_tracked + 1
+                if self.momentum is None:
+                    exponential_average_factor = 1.0 / float(self.num_batches_tracked)
+                else:
+                    exponential_average_factor = self.momentum
+        if self.training:
+            bn_training = True
+        else:
+            bn_training = (self.running_mean is None) and (self.running_var is None)
+        passed_running_mean = self.running_mean if not self.training or self.track_running_stats else None
+        passed_running_var = self.running_var if not self.training or self.track_running_stats else None
+        self.last_path = "torch"
+        if passed_running_mean is None:
+            return F.batch_norm(input, passed_running_mean, passed_running_var, self.weight, self.bias, bn_training,
+                                exponential_average_factor, self.eps)
+        input_var = input.permute([1, 0, 2, 3]).reshape(input.shape[1], input.shape[0] * input.shape[2] * input.shape[3]).var(axis=1, unbiased=False)
+        input_mean = input.mean(axis=3).mean(axis=2).mean(0)
+        source_stat_factor = torch.true_divide(self.num_batches_tracked, (self.num_batches_tracked + torch.tensor(1)))
+        batch_stat_factor = torch.true_divide(torch.tensor(1), (self.num_batches_tracked + torch.tensor(1)))
+        mean_to_use = source_stat_factor * passed_running_mean + batch_stat_factor * input_mean
+        var_to_use = source_stat_factor * passed_running_var + batch_stat_factor * input_var
+        return F.batch_norm(input, mean_to_use, var_to_use, self.weight, self.bias, False, 0.0, self.eps)
+
+    # ---- entry points ----------------------------------------------------------------------------------------------------------
+    def forward(self, input):
+        if not self.mode_one:
+            return super().forward(input)
+        if self._hip_ok(input):
+            return self._mode_one_hip_(input.clone(memory_format=torch.channels_last))
+        return self._mode_one_torch(input)
+
+    def forward_fused_(self, x, residual=None, relu=False):
+        """act(self(x) (+ residual)), in place on x where the HIP path applies (x: a fresh convolution output nothing else holds)."""
+        if self.mode_one and self._hip_ok(x, residual):
+            return self._mode_one_hip_(x, residual, relu)
+        y = self(x)
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if relu else y

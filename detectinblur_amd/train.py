@@ -57,7 +57,7 @@ def seed_everything(distributed):
 # lines are accepted unchanged) and raise only when actually set.
 _OUT_OF_SCOPE = {"deblur_first": "the deblur-first pipeline (DeepDeblur)", "non_pos_aug_mix": "AugMix",
                  "include_pos_aug_mix": "AugMix", "aug_mix_target_expand": "AugMix",
-                 "unfrozen_batch_norm": "trainable batch-norm conversion", "mode_one_norm": "the custom BatchNorm remedy",
+                 "unfrozen_batch_norm": "trainable batch-norm conversion",
                  "blurred_dataset": "real-blur datasets (GOPRO / REDS)", "expand_synth_boxes": "real-blur datasets (GOPRO / REDS)"}
 
 

@@ -3,6 +3,8 @@
   * expand_targets / fix_bounding_box_squeeze   reference utils.py:360-434  (HIP, one launch/image)
   * get_norm_params                              reference utils.py:219-273  (host tables)
   * collate_fn, distributed helpers, meters      reference utils.py:474-785  (below)
+  * convert_to_custom_batch_norm, set_batch_norm_N, set_batch_norm_mode1
+                                                 reference utils.py:59-77, :122-135, :150-162 (--mode_one_norm)
 """
 import numpy as np
 import os
@@ -10,6 +12,80 @@ import os
 import torch
 
 from . import blur_ops
+
+# ---------------------------------------------------------------------------------------------
+# test-time batch-norm (--mode_one_norm)
+# ---------------------------------------------------------------------------------------------
+
+# what the inference trunk caches about its batch-norm layers (models/backbone.py, models/generalized_rcnn.py): captured graphs,
+# the tensors and pointers they were captured over, the (convolution, batch-norm) pairs and refresh_folded's version watch
+# and, per convolution, the folds of its frozen batch-norm
+_TRUNK_CACHES = ("_trunk_graphs", "_trunk_tensors", "_trunk_ptrs", "_dib_fold_pairs", "_dib_fold_watch", "_dib_fold_state", "_dib_fold",
+                 "_dib_fold_planar")
+
+
+def _drop_trunk_caches(model):
+    """A layer swap, a new num_batches_tracked or a mode switch changes what the trunk computes: without this a model evaluated
+    once would replay a graph captured with the old layers (GeneralizedRCNN._sync_graphs_with_weights watches the OLD tensors)."""
+    for m in model.modules():
+        for key in _TRUNK_CACHES:
+            m.__dict__.pop(key, None)
+
+
+def _is_bn(module):
+    from .models.batchnorm import BatchNorm2d
+    return isinstance(module, (torch.nn.modules.batchnorm._BatchNorm, BatchNorm2d))
+
+
+def convert_to_custom_batch_norm(model, batch_norm_to_use):
+    """Every FrozenBatchNorm2d under `model` becomes `batch_norm_to_use(num_features, momentum=0.1, affine=True,
+    track_running_stats=True)` (eps: that constructor's default, 1e-5): weight and bias as Parameters over the frozen layer's
+    tensors, running statistics cloned.  Reference utils.py:59-77; the one difference: num_batches_tracked is placed on the
+    running statistics' device, so that the HIP path reads it there (no host synchronisation).  Returns `model`."""
+    from .models.backbone import FrozenBatchNorm2d
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = convert_to_custom_batch_norm(module, batch_norm_to_use)
+        if type(module) == FrozenBatchNorm2d:
+            num_features = module.running_mean.shape[0]
+            layer_new = batch_norm_to_use(num_features, momentum=0.1, affine=True, track_running_stats=True)
+            layer_new.weight = torch.nn.Parameter(module.weight)
+            layer_new.bias = torch.nn.Parameter(module.bias)
+            layer_new.running_mean = module.running_mean.clone().detach()
+            layer_new.running_var = module.running_var.clone().detach()
+            if getattr(layer_new, "num_batches_tracked", None) is not None:
+                layer_new.num_batches_tracked = layer_new.num_batches_tracked.to(module.running_mean.device)
+            model._modules[name] = layer_new
+    _drop_trunk_caches(model)
+    return model
+
+
+def set_batch_norm_mode1(model, flag):
+    """`mode_one = flag` on every batch-norm layer under `model` (reference utils.py:122-135).  Returns `model`."""
+    if _is_bn(model):
+        model.mode_one = flag
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = set_batch_norm_mode1(module, flag)
+        if _is_bn(module):
+            module.mode_one = flag
+    _drop_trunk_caches(model)
+    return model
+
+
+def set_batch_norm_N(model, N):
+    """num_batches_tracked += N on every batch-norm layer under `model` (a new tensor on the old one's device; reference
+    utils.py:150-162).  Returns `model`."""
+    if _is_bn(model):
+        model.num_batches_tracked = model.num_batches_tracked + N
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = set_batch_norm_N(module, N)
+        if _is_bn(module):
+            module.num_batches_tracked = module.num_batches_tracked + N
+    _drop_trunk_caches(model)
+    return model
+
 
 # ---------------------------------------------------------------------------------------------
 # boxes

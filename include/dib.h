@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more: DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
+#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
                              per-tap offset array (sizes come from dib_tap_table_bytes as before)          */
 
 /* error codes */
@@ -424,6 +424,24 @@ int dib_post_ops(const void *in_dev, void *out_dev, int C, int H, int W, int dty
  * quantisation step of the reference's (tests/test_jpeg.py), as torch's own GPU path is. */
 int dib_jpeg_roundtrip(const void *in_dev, void *out_dev, int H, int W, int dtype, const float *q_luma,
                        const float *q_chroma, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Test-time batch-norm statistics, the reference's `--mode_one_norm` (models/batchnorm.py:159-184): every batch-norm layer
+ * of the trunk normalises with its running statistics mixed with those of the batch it sees,
+ *   mean = f * running_mean + g * mean_b,  var = f * running_var + g * var_b   (biased batch variance over N * H * W),
+ *   f = float(n) / float(n + 1),  g = 1 / float(n + 1),  n = num_batches_tracked,
+ *   x = act(x * scale[c] + shift[c] (+ residual)),  scale = w / sqrt(var + eps),  shift = b - mean * scale,
+ * in place on a channels-last fp32 activation x_dev [n_pix][C] (C % 4 == 0; x, residual and workspace 16-byte aligned).
+ * weight_dev / bias_dev may be NULL (1 and 0).  n comes from num_batches_dev (one int64 on the device, read there) or, when
+ * that is NULL, from num_batches.  workspace_dev: dib_bn_mode_one_workspace_bytes(n_pix, C) bytes of device memory, no
+ * initial contents needed (0: bad shape).  stats_dev, optional: [2][C] floats, the mixed mean and variance.  Three launches,
+ * no atomics, no host synchronisation: deterministic and capturable into a graph.
+ * ------------------------------------------------------------------------------------- */
+size_t dib_bn_mode_one_workspace_bytes(long long n_pix, int C);
+int dib_bn_mode_one_nhwc(float *x_dev, const float *residual_dev, long long n_pix, int C, const float *weight_dev, const float *bias_dev,
+                         const float *running_mean_dev, const float *running_var_dev, const long long *num_batches_dev,
+                         long long num_batches, float eps, int relu, void *workspace_dev, size_t workspace_bytes, float *stats_dev,
+                         void *stream);
 
 #ifdef __cplusplus
 }

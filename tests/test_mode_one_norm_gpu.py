@@ -1,0 +1,243 @@
+"""`--mode_one_norm` on the MI355X: the HIP path of models/batchnorm.BatchNorm2d (csrc/dib_bnstats.hip) against float64 on the
+53 trunk shapes at batch 1, 800 x 1344 (and N = 2), against the fixture's reference outputs, and bitwise against itself; the
+converted detector (every layer on the HIP path, close to the torch path, graphed == eager, conversion after a frozen
+evaluation == a fresh conversion); and evaluate.main --mode_one_norm reproducible across two fresh processes."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from detectinblur_amd import utils
+from detectinblur_amd.models import backbone
+from detectinblur_amd.models.batchnorm import BatchNorm2d
+
+pytestmark = pytest.mark.gpu
+
+N_TRACKED = 16
+
+
+def _trunk_shapes():
+    """(C, H, W, residual, relu) of the 53 batch-norm layers of ResNet-50 at 800 x 1344 (stem, then stage by stage)."""
+    out = [(64, 400, 672, False, True)]
+    hw = (200, 336)
+    for planes, blocks, stride in ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)):
+        H, W = hw
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        for b in range(blocks):
+            hin = (H, W) if b == 0 else (Ho, Wo)
+            out.append((planes, hin[0], hin[1], False, True))          # bn1 behind the 1x1
+            out.append((planes, Ho, Wo, False, True))                  # bn2 behind the (strided) 3x3
+            out.append((planes * 4, Ho, Wo, True, True))               # bn3: + identity, ReLU
+            if b == 0:
+                out.append((planes * 4, Ho, Wo, False, False))         # downsample
+        hw = (Ho, Wo)
+    assert len(out) == 53
+    return out
+
+
+SHAPES = sorted(set(_trunk_shapes()))
+
+
+def _layer(C, dev, seed):
+    g = torch.Generator().manual_seed(seed)
+    bn = BatchNorm2d(C)
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(C, generator=g) + 0.5)
+        bn.bias.copy_(torch.rand(C, generator=g) - 0.5)
+        bn.running_mean.copy_(torch.randn(C, generator=g))
+        bn.running_var.copy_(torch.rand(C, generator=g) * 2 + 0.2)
+    bn.num_batches_tracked = bn.num_batches_tracked + N_TRACKED
+    bn.mode_one = True
+    return bn.to(dev).eval()
+
+
+def _activation(N, C, H, W, dev, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    mean = torch.randn((1, C, 1, 1), generator=g, device=dev) * 3
+    std = torch.rand((1, C, 1, 1), generator=g, device=dev) * 2 + 0.1
+    x = torch.randn((N, C, H, W), generator=g, device=dev) * std + mean
+    return x.contiguous(memory_format=torch.channels_last)
+
+
+def _f64(bn, x, res, relu):
+    x64 = x.double()
+    C = x.shape[1]
+    xs = x64.permute(1, 0, 2, 3).reshape(C, -1)
+    mb, vb = xs.mean(1), xs.var(1, unbiased=False)
+    n = float(bn.num_batches_tracked)
+    f, g = n / (n + 1), 1 / (n + 1)
+    mean = f * bn.running_mean.double() + g * mb
+    var = f * bn.running_var.double() + g * vb
+    scale = bn.weight.double() / torch.sqrt(var + bn.eps)
+    y = (x64 - mean.view(1, -1, 1, 1)) * scale.view(1, -1, 1, 1) + bn.bias.double().view(1, -1, 1, 1)
+    if res is not None:
+        y = y + res.double()
+    if relu:
+        y = y.clamp_min(0)
+    return mean, var, y
+
+
+@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "C%d_%dx%d%s%s" % (s[0], s[1], s[2], "_res" if s[3] else "", "_relu" if s[4] else ""))
+def test_kernel_against_float64_on_the_trunk_shapes(shape, N):
+    C, H, W, has_res, relu = shape
+    if N == 2 and C * H * W > 256 * 200 * 336:
+        pytest.skip("N = 2 is covered from layer1 down")
+    dev = torch.device("cuda")
+    bn = _layer(C, dev, C + H)
+    x = _activation(N, C, H, W, dev, 7 * C + W)
+    for res_on, relu_on in {(has_res, relu), (False, False), (True, True)}:
+        res = _activation(N, C, H, W, dev, 11 * C + H) if res_on else None
+        stats = torch.empty((2, C), dtype=torch.float32, device=dev)
+        y = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last), res, relu_on, stats)
+        y2 = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last), res, relu_on)
+        torch.cuda.synchronize()
+        assert torch.equal(y, y2), "two calls on the same input differ"
+        mean64, var64, y64 = _f64(bn, x, res, relu_on)
+        sd = var64.sqrt()
+        # the mean: 1e-5 sigma, or two fp32 ulps of |mean| where that is larger (the mixed mean is ONE fp32 number)
+        assert bool(((stats[0].double() - mean64).abs() <= 1e-5 * sd + 2.4e-7 * mean64.abs()).all())
+        assert bool(((stats[1].double() - var64).abs() <= 1e-5 * var64).all())
+        err = (y.detach().double() - y64).abs() / (1 + y64.abs())
+        assert float(err.max()) <= 1e-4, float(err.max())
+
+
+def test_kernel_against_the_fixture():
+    from tests.test_mode_one_norm import CASES, fixture_case, load_fixture
+    fx = load_fixture()
+    dev = torch.device("cuda")
+    for name, *_ in CASES:
+        d = fixture_case(fx, name)
+        C = d["running_mean"].shape[0]
+        bn = BatchNorm2d(C)
+        with torch.no_grad():
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                getattr(bn, k).copy_(torch.from_numpy(d[k]))
+        bn.num_batches_tracked = bn.num_batches_tracked + int(fx["num_batches_tracked"])
+        bn.mode_one = True
+        bn = bn.to(dev).eval()
+        x = torch.from_numpy(d["x"]).to(dev).contiguous(memory_format=torch.channels_last)
+        stats = torch.empty((2, C), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            y = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last), None, False, stats)
+            y_mod = bn(x)
+        assert bn.last_path == "hip"
+        assert torch.equal(y, y_mod)
+        y = y.cpu().double().numpy()
+        y64, y_ref = fx[name + "/y64"], fx[name + "/y_ref"].astype(np.float64)
+        assert np.all(np.abs(y - y64) <= 1e-4 * (1 + np.abs(y64))), name
+        assert np.all(np.abs(y - y_ref) <= 1e-4 * (1 + np.abs(y_ref))), name
+        var64 = fx[name + "/var64"]
+        assert np.all(np.abs(stats[1].cpu().double().numpy() - var64) <= 1e-5 * var64), name      # incl. |mean| ~ 1e3 sigma
+
+
+def test_num_batches_tracked_on_the_host_or_the_device():
+    dev = torch.device("cuda")
+    bn = _layer(64, dev, 3)
+    x = _activation(1, 64, 30, 40, dev, 4)
+    a = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last))
+    bn.num_batches_tracked = bn.num_batches_tracked.cpu()
+    b = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last))
+    assert torch.equal(a, b)
+
+
+# ---- the converted detector ----------------------------------------------------------------------------------------------------------
+
+def _detector():
+    from detectinblur_amd.models.faster_rcnn import fasterrcnn_resnet50_fpn
+    torch.manual_seed(0)
+    m = fasterrcnn_resnet50_fpn(num_classes=91, pretrained=False, pretrained_backbone=False)
+    g = torch.Generator().manual_seed(1)
+    for mod in m.modules():
+        if isinstance(mod, backbone.FrozenBatchNorm2d):
+            C = mod.weight.shape[0]
+            mod.weight.copy_(torch.rand(C, generator=g) + 0.5)
+            mod.bias.copy_(torch.rand(C, generator=g) - 0.5)
+            mod.running_mean.copy_(torch.rand(C, generator=g) - 0.5)
+            mod.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+    return m.to("cuda").eval()
+
+
+def _convert(m):
+    m = utils.convert_to_custom_batch_norm(m, batch_norm_to_use=BatchNorm2d)
+    m = utils.set_batch_norm_N(m, 16)
+    m = utils.set_batch_norm_mode1(m, True)
+    return m.eval()           # the new layers start in training mode, where the reference also bumps num_batches_tracked
+
+
+def _image():
+    g = torch.Generator().manual_seed(2)
+    return torch.rand((3, 800, 1333), generator=g).cuda()
+
+
+def _features(m, img):
+    with torch.no_grad():
+        batch, _ = m.transform([img])
+        return m.backbone(batch.tensors)
+
+
+def test_converted_trunk_runs_every_layer_on_the_hip_path_close_to_the_torch_path():
+    m = _convert(_detector())
+    img = _image()
+    bns = [b for b in m.modules() if isinstance(b, BatchNorm2d)]
+    assert len(bns) == 53
+    for b in bns:
+        b.last_path = None
+    fast = _features(m, img)
+    assert [b.last_path for b in bns] == ["hip"] * 53
+    assert all(b.num_batches_tracked.is_cuda for b in bns)
+    old = backbone.FUSE_TEST_TIME_BN
+    backbone.FUSE_TEST_TIME_BN = False
+    try:
+        slow = _features(m, img)
+    finally:
+        backbone.FUSE_TEST_TIME_BN = old
+    assert [b.last_path for b in bns] == ["torch"] * 53
+    for k in fast:
+        rel = float((fast[k] - slow[k]).abs().max()) / float(slow[k].abs().max())
+        assert rel <= 1e-3, (k, rel)
+
+
+def _detections(m, img, graphed):
+    m.graph_inference = graphed
+    with torch.no_grad():
+        outs = [m([img])[0] for _ in range(3)]        # the graph cache captures on a later sighting
+    torch.cuda.synchronize()
+    return outs[-1]
+
+
+def test_graphed_trunk_equals_eager_and_conversion_after_a_frozen_run_equals_a_fresh_one():
+    img = _image()
+    fresh = _convert(_detector())
+    eager = _detections(fresh, img, False)
+    graphed = _detections(fresh, img, True)
+    assert "_trunk_graphs" in fresh.__dict__
+    for k in ("boxes", "scores", "labels"):
+        assert torch.equal(eager[k], graphed[k]), k
+    late = _detector()
+    frozen = _detections(late, img, True)                 # captured with frozen batch-norm
+    late = _convert(late)
+    again = _detections(late, img, True)
+    for k in ("boxes", "scores", "labels"):
+        assert torch.equal(again[k], graphed[k]), k
+    assert not (frozen["boxes"].shape == again["boxes"].shape and torch.equal(frozen["boxes"], again["boxes"]))
+
+
+# ---- driver ----------------------------------------------------------------------------------------------------------------------------
+
+def evaluate_main_digest_child(out_path, argv):
+    from tests import _gpu_children
+    _gpu_children._guarded(_gpu_children._evaluate_main_digest, out_path, (argv,))
+
+
+def test_two_runs_of_evaluate_main_mode_one_print_identical_coco_stats(tmp_path):
+    from tests.test_ddp_gpu import _run_child
+    argv = ["--synthetic", "--synthetic_images", "3", "--mode_one_norm", "--blur_eval", "--gpu_blur", "--early_stop", "3"]
+    (tmp_path / "a").mkdir(); (tmp_path / "b").mkdir()
+    a = _run_child(evaluate_main_digest_child, tmp_path / "a", argv)
+    b = _run_child(evaluate_main_digest_child, tmp_path / "b", argv)
+    assert len(a["stat_lines"]) == 12 * 15
+    assert a["stat_lines"] == b["stat_lines"]
+    for cell in a["cells"]:
+        assert a["cells"][cell] == b["cells"][cell], cell
