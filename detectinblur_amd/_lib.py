@@ -27,6 +27,17 @@ _lib = None
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
+
+class AugmixImage(ctypes.Structure):
+    """include/dib.h dib_augmix_image: one image's AugMix plan for dib_augmix."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("buf_offset", ctypes.c_ulonglong), ("H", ctypes.c_int),
+                ("W", ctypes.c_int), ("flip", ctypes.c_int), ("n_ops", ctypes.c_int * 3), ("op", (ctypes.c_int * 3) * 3),
+                ("iparam", (ctypes.c_int * 3) * 3), ("affine", ((ctypes.c_double * 6) * 3) * 3), ("ws", ctypes.c_float * 3),
+                ("m", ctypes.c_float), ("one_minus_m", ctypes.c_float)]
+
+
+_c_augmix_p = ctypes.POINTER(AugmixImage)
+
 _SIGNATURES = {
     "dib_abi_version": (ctypes.c_int, []),
     "dib_last_error": (ctypes.c_char_p, []),
@@ -129,6 +140,10 @@ _SIGNATURES = {
     "dib_bn_mode_one_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_augmix_buffer_bytes": (ctypes.c_ulonglong, [_c_augmix_p]),
+    "dib_augmix_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_ulonglong]),
+    "dib_augmix": (ctypes.c_int, [_c_augmix_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     # test hook, not part of the drop-in boundary
     "dib_sparse_blur_generic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

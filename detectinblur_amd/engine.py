@@ -60,11 +60,25 @@ def _adopt(out, staged, device):
     return out
 
 
+def _augmix_plan(blur_dict):
+    plan = blur_dict.get("augmix") if isinstance(blur_dict, dict) else None
+    return plan if plan is not None and plan["deferred"] else None
+
+
 def _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, cuda):
+    plans = [_augmix_plan(bd) for bd in blur_dicts]
     if cuda:
-        images_GPU = [image.to(device, non_blocking=True).half() for image in images_CPU]
+        uploaded = [image.to(device, non_blocking=True) for image in images_CPU]
+        images_GPU = [u.half() if p is None else None for u, p in zip(uploaded, plans)]
+        todo = [i for i, p in enumerate(plans) if p is not None]
+        if todo:
+            # AugMix planned by the loader (transforms.AugMix(defer=True)): one batched HIP pass writes the fp16 images
+            from . import augmix
+            for i, out in zip(todo, augmix.apply_plans_device([uploaded[i] for i in todo], [plans[i] for i in todo])):
+                images_GPU[i] = out
     else:
-        images_GPU = [image.half() for image in images_CPU]
+        from . import augmix
+        images_GPU = [(image if p is None else augmix.apply_deferred_host(image, p)).half() for image, p in zip(images_CPU, plans)]
     targets_GPU = [{k: (v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in t.items()} for t in targets]
     psfs_GPU = thetas = l1 = l2 = tables = None
     if blurring:

@@ -7,7 +7,7 @@ One process per GPU, DistributedDataParallel over RCCL (backend "nccl" on ROCm),
 SGD(lr 0.04, momentum 0.9, wd 1e-4) + MultiStepLR, seeds rank*1337, per-epoch checkpoints
 {'model','optimizer','lr_scheduler','args','epoch'} and --resume / --start_from_weights
 (reference train.py:89-391), TensorBoard scalars under --tensorboard_path.  The reference's README command
-lines parse unchanged; flags of subsystems outside the built path (AugMix, deblur-first, custom BN, real-blur
+lines parse unchanged; flags of subsystems outside the built path (deblur-first, custom BN, real-blur
 datasets) are accepted and refused with a clear message only when set.
 """
 import argparse
@@ -29,9 +29,15 @@ from .models.faster_rcnn import fasterrcnn_resnet50_fpn
 
 def get_transform(train, blur=False, blur_type=None, blur_ratio=0.5, use_stored_psfs=False, cpu_blur=False,
                   stored_psf_directory=None, dont_center_psf=False, low_exposure=False, high_exposure=False,
-                  blur_exposure=None, stored_psf_count=T.STORED_PSF_COUNT, LEHE_blur_seg=False, dilate_psf=False):
-    """reference train.py:48-86: [BlurImage] -> ToTensor -> [RandomHorizontalFlip(0.5) when training]."""
+                  blur_exposure=None, stored_psf_count=T.STORED_PSF_COUNT, LEHE_blur_seg=False, dilate_psf=False,
+                  non_pos_aug_mix=False, include_pos_aug_mix=False, aug_mix_target_expand=False, defer_aug_mix=False):
+    """reference train.py:48-86: [AugMix] -> [BlurImage] -> ToTensor -> [RandomHorizontalFlip(0.5) when training].
+    `defer_aug_mix` (this repo): AugMix's pixels are left to the GPU (engine._stage); never with `cpu_blur`, whose FFT blur in the
+    loader needs the augmented image."""
     tf = []
+    if non_pos_aug_mix:
+        tf.append(T.AugMix(include_pos_aug_mix=include_pos_aug_mix, modify_target_boxes=aug_mix_target_expand,
+                           defer=defer_aug_mix and not cpu_blur))
     if blur:
         tf.append(T.BlurImage(prob=blur_ratio, blur_type=blur_type, blur_exposure=blur_exposure, use_stored_psfs=use_stored_psfs,
                               stored_psf_directory=stored_psf_directory, blur_image_in_transform=cpu_blur,
@@ -55,8 +61,7 @@ def seed_everything(distributed):
 
 # Flags of subsystems SURVEY.md section 2 places outside the built path: they parse (the reference's command
 # lines are accepted unchanged) and raise only when actually set.
-_OUT_OF_SCOPE = {"deblur_first": "the deblur-first pipeline (DeepDeblur)", "non_pos_aug_mix": "AugMix",
-                 "include_pos_aug_mix": "AugMix", "aug_mix_target_expand": "AugMix",
+_OUT_OF_SCOPE = {"deblur_first": "the deblur-first pipeline (DeepDeblur)",
                  "unfrozen_batch_norm": "trainable batch-norm conversion",
                  "blurred_dataset": "real-blur datasets (GOPRO / REDS)", "expand_synth_boxes": "real-blur datasets (GOPRO / REDS)"}
 
@@ -112,9 +117,10 @@ def add_shared_flags(p):
     # outside the built path: accepted, refused when set (reject_out_of_scope)
     p.add_argument("--deblur_first", action="store_true", help="(not built) deblur before detecting")
     p.add_argument("--deblurer_model_location", default=None, help="(not built)")
-    p.add_argument("--non_pos_aug_mix", action="store_true", help="(not built) AugMix")
-    p.add_argument("--include_pos_aug_mix", action="store_true", help="(not built) AugMix")
-    p.add_argument("--aug_mix_target_expand", action="store_true", help="(not built) AugMix")
+    p.add_argument("--non_pos_aug_mix", action="store_true", help="Non positional augmix (training only; pixels on the GPU unless --cpu_blur).")
+    p.add_argument("--include_pos_aug_mix", action="store_true", help="Include positional augmentations in augmix (with --non_pos_aug_mix).")
+    p.add_argument("--aug_mix_target_expand", action="store_true",
+                   help="Expand target boxes for AugMix according to positional shifts from spatial augmentations.")
     p.add_argument("--unfrozen_batch_norm", action="store_true", help="(not built)")
     p.add_argument("--world-size", default=1, type=int, help="number of distributed processes")
     p.add_argument("--dist-url", default="env://", help="url used to set up distributed training")
@@ -183,8 +189,11 @@ def main(args):
     common = dict(use_stored_psfs=args.use_stored_psfs, cpu_blur=args.cpu_blur,
                   stored_psf_directory=args.stored_psf_directory, dont_center_psf=args.dont_center_psf,
                   high_exposure=args.high_exposure, low_exposure=args.low_exposure, stored_psf_count=args.stored_psf_count)
+    aug_mix = dict(non_pos_aug_mix=args.non_pos_aug_mix, include_pos_aug_mix=args.include_pos_aug_mix,
+                   aug_mix_target_expand=args.aug_mix_target_expand, defer_aug_mix=device.type == "cuda")
     dataset, num_classes = get_coco(args.data_path, "train", get_transform(True, blur=args.blur_train, blur_type=blur_type,
-                                                                           blur_ratio=blur_ratio, **common), synthetic=synthetic, with_masks=args.with_masks)
+                                                                           blur_ratio=blur_ratio, **common, **aug_mix),
+                                    synthetic=synthetic, with_masks=args.with_masks)
     dataset_test, _ = get_coco(args.data_path, "val", get_transform(False, blur=False), synthetic=synthetic, with_masks=args.with_masks)
     eval_blur_type = blur_type if (args.high_exposure and not args.low_exposure) else None        # :164-169
     dataset_test_blur, _ = get_coco(args.data_path, "val", get_transform(False, blur=True, blur_ratio=1, blur_type=eval_blur_type,

@@ -63,6 +63,44 @@ class RandomHorizontalFlip(object):
                 target["masks"] = target["masks"].flip(-1)
             if "keypoints" in target:
                 target["keypoints"] = _flip_coco_person_keypoints(target["keypoints"], width)
+            plan = blur_dict.get("augmix") if isinstance(blur_dict, dict) else None
+            if plan is not None and plan["deferred"]:       # AugMix still to come on the GPU: it must mirror its result
+                plan["flip"] = not plan["flip"]
+        return image, target, blur_dict
+
+
+class AugMix(object):
+    """reference transforms.py:68-79: one Python-`random` draw (always under 1.1), then augment_and_mix's draws and box mapping on
+    the host (augmix.draw_plan).  The plan goes into blur_dict["augmix"].  `defer` (this repo): leave the pixels to the GPU
+    (engine._stage -> augmix.apply_plans_device); the image stays what the loader gave, as k / 255 values.  Without it the plan
+    is applied here with the reference's Pillow operations (--cpu_blur, which blurs the augmented image in the loader, and CPU
+    runs) and a PIL image comes back, as in the reference."""
+
+    def __init__(self, prob=1.1, include_pos_aug_mix=False, modify_target_boxes=False, defer=False):
+        self.prob = prob
+        self.include_pos_aug_mix = include_pos_aug_mix
+        self.modify_target_boxes = modify_target_boxes
+        self.defer = defer
+
+    def __call__(self, image, target, blur_dict={}):
+        from . import augmix
+        if random.random() < self.prob:
+            if self.defer and isinstance(image, torch.Tensor):
+                H, W = image.shape[-2:]
+            elif self.defer and hasattr(image, "size") and not isinstance(image, np.ndarray):
+                W, H = image.size
+            else:
+                img = augmix.to_uint8_hwc(image)
+                H, W = img.shape[:2]
+            plan, target = augmix.draw_plan(H, W, self.include_pos_aug_mix, target, self.modify_target_boxes)
+            if self.defer:
+                plan["deferred"] = True
+                if isinstance(image, torch.Tensor):      # the uint8 image the PIL form holds, as ToTensor would give it
+                    image = (image * 255).to(torch.uint8).to(torch.float32).div(255)
+            else:
+                from PIL import Image
+                image = Image.fromarray(augmix.apply_plan(img, plan))
+            blur_dict["augmix"] = plan
         return image, target, blur_dict
 
 

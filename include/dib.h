@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
+#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
                              per-tap offset array (sizes come from dib_tap_table_bytes as before)          */
 
 /* error codes */
@@ -442,6 +442,49 @@ int dib_bn_mode_one_nhwc(float *x_dev, const float *residual_dev, long long n_pi
                          const float *running_mean_dev, const float *running_var_dev, const long long *num_batches_dev,
                          long long num_batches, float eps, int relu, void *workspace_dev, size_t workspace_bytes, float *stats_dev,
                          void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * AugMix on the device (reference transforms.py:68-79, augmix/augment_and_mix.py:123-185), from plans drawn on the host
+ * (transforms.AugMix): per image three chains of up to three ops, Pillow's semantics on uint8 images, then the reference's
+ * float64 mix with the COCO mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225), written as fp16.
+ * Op codes follow the reference's `augmentations` list; iparam: posterize bits (1..8) / solarize threshold (0..256); affine:
+ * Pillow's inverse affine coefficients (a0..a5: source x = a0 (x + .5) + a1 (y + .5) + a2, y likewise) of a positional op.
+ * src: 3 x H x W fp32 planes holding k / 255 (k = 0..255), mirrored left-right when flip != 0 (the result is then mirrored too);
+ * dst: 3 x H x W fp16 planes, must not alias src.  buf_offset: byte offset of the image's uint8 stage images inside the
+ * workspace's buffer area (dib_augmix_buffer_bytes(plan) bytes each; regions of different images must not overlap).
+ * plans_host and plans_dev hold the same n records (the host copy is read during the call for validation and launch sizes).
+ * norm_table_dev: [3][256] doubles (k / 255 - mean_c) / std_c; scale_table_dev: [256] doubles 255.0 / d (entry 0 unused);
+ * half_table_dev: [256] fp16 bits of float(k) / 255.  workspace_dev: dib_augmix_workspace_bytes(n, sum of the buffer bytes)
+ * bytes, no initial contents needed.  No atomics outside LDS, no host synchronisation: deterministic and capturable.
+ * ------------------------------------------------------------------------------------- */
+#define DIB_AUGMIX_WIDTH 3
+#define DIB_AUGMIX_MAX_DEPTH 3
+#define DIB_AUGMIX_AUTOCONTRAST 0
+#define DIB_AUGMIX_EQUALIZE 1
+#define DIB_AUGMIX_POSTERIZE 2
+#define DIB_AUGMIX_ROTATE 3
+#define DIB_AUGMIX_SOLARIZE 4
+#define DIB_AUGMIX_SHEAR_X 5
+#define DIB_AUGMIX_SHEAR_Y 6
+#define DIB_AUGMIX_TRANSLATE_X 7
+#define DIB_AUGMIX_TRANSLATE_Y 8
+typedef struct dib_augmix_image {
+  const float *src;
+  void *dst;
+  unsigned long long buf_offset;
+  int H, W, flip;
+  int n_ops[DIB_AUGMIX_WIDTH];
+  int op[DIB_AUGMIX_WIDTH][DIB_AUGMIX_MAX_DEPTH];
+  int iparam[DIB_AUGMIX_WIDTH][DIB_AUGMIX_MAX_DEPTH];
+  double affine[DIB_AUGMIX_WIDTH][DIB_AUGMIX_MAX_DEPTH][6];
+  float ws[DIB_AUGMIX_WIDTH];
+  float m, one_minus_m;  /* m and float32(1 - m), as numpy computes them */
+} dib_augmix_image;
+unsigned long long dib_augmix_buffer_bytes(const dib_augmix_image *plan);
+size_t dib_augmix_workspace_bytes(int n_images, unsigned long long buffer_bytes);
+int dib_augmix(const dib_augmix_image *plans_host, const dib_augmix_image *plans_dev, int n_images, const double *norm_table_dev,
+               const double *scale_table_dev, const unsigned short *half_table_dev, void *workspace_dev, size_t workspace_bytes,
+               void *stream);
 
 #ifdef __cplusplus
 }
