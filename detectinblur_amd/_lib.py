@@ -129,6 +129,21 @@ _SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "dib_stem_pool_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_void_p]),
+    # bf16 forms (same argument lists as the fp32 entries above)
+    "dib_bias_act_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_void_p]),
+    "dib_bias_act_mask_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_relu_mask_backward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "dib_add_relu_mask_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "dib_scatter_add_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "dib_fpn_topdown_merge_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "dib_stem_pool_forward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "dib_stem_pool_backward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_void_p]),
     "dib_fold_bn_multi": (ctypes.c_int, [_c_void_pp, _c_void_pp, _c_void_pp, _c_void_pp, _c_void_pp, _c_int_p, _c_int_p, ctypes.c_int,
                                          ctypes.c_float, _c_void_pp, _c_void_pp, _c_void_pp, ctypes.c_void_p]),
     "dib_scale_rows_multi": (ctypes.c_int, [_c_void_pp, _c_void_pp, _c_int_p, _c_int_p, ctypes.c_int, _c_void_pp, ctypes.c_void_p]),

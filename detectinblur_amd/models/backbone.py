@@ -65,16 +65,21 @@ class _BiasAct(torch.autograd.Function):
         stream = _lib.stream_of(x)
         res = residual.data_ptr() if residual is not None else None
         ctx.relu, ctx.has_res, ctx.masked, ctx.state = bool(relu), residual is not None, False, state
+        lp = x.dtype == torch.bfloat16       # bf16 activation, fp32 bias: the 8-per-lane kernels (bias_act checked C % 8 and alignment)
+        if lp:
+            LP_CALLS["bias_act"] += 1
         if (relu and RELU_MASK and any(ctx.needs_input_grad[:3]) and C % 4 == 0
                 and not ((x.data_ptr() | bias.data_ptr() | (res or 0)) & 15)):
-            mask = torch.empty(x.numel() // 4, dtype=torch.uint8, device=x.device)
-            _lib.check(_lib.lib().dib_bias_act_mask_nhwc(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, mask.data_ptr(), stream))
+            mask = torch.empty(x.numel() // (8 if lp else 4), dtype=torch.uint8, device=x.device)
+            fn = _lib.lib().dib_bias_act_mask_bf16_nhwc if lp else _lib.lib().dib_bias_act_mask_nhwc
+            _lib.check(fn(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, mask.data_ptr(), stream))
             ctx.masked = True
             ctx.save_for_backward(mask)
             if state is not None:
                 state["mask"] = mask
         else:
-            _lib.check(_lib.lib().dib_bias_act_nhwc(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, int(relu), stream))
+            fn = _lib.lib().dib_bias_act_bf16_nhwc if lp else _lib.lib().dib_bias_act_nhwc
+            _lib.check(fn(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, int(relu), stream))
             if relu:
                 ctx.save_for_backward(x)
         ctx.mark_dirty(x)
@@ -95,32 +100,59 @@ class _BiasAct(torch.autograd.Function):
             if grad.data_ptr() & 15:
                 grad = grad.clone(memory_format=torch.channels_last)
             out = torch.empty_like(grad)     # not in place: autograd may hand the same gradient tensor to another node
-            _lib.check(_lib.lib().dib_relu_mask_backward(grad.data_ptr(), mask.data_ptr(), out.data_ptr(), grad.numel(),
-                                                         _lib.stream_of(grad)))
+            fn = _lib.lib().dib_relu_mask_backward_bf16 if grad.dtype == torch.bfloat16 else _lib.lib().dib_relu_mask_backward
+            _lib.check(fn(grad.data_ptr(), mask.data_ptr(), out.data_ptr(), grad.numel(), _lib.stream_of(grad)))
             grad = out
         elif ctx.relu:
             (y,) = ctx.saved_tensors
             grad = torch.ops.aten.threshold_backward(grad, y, 0)
-        gb = grad.sum(dim=(0, 2, 3)) if ctx.needs_input_grad[1] else None
+        gb = _channel_sum(grad) if ctx.needs_input_grad[1] else None
         return grad, gb, (grad if ctx.has_res else None), None, None
+
+
+def _channel_sum(grad):
+    """Bias gradient of a [N, C, H, W] gradient; a bf16 gradient is summed into an fp32 result (the bias is fp32)."""
+    if grad.dtype == torch.float32:
+        return grad.sum(dim=(0, 2, 3))
+    return grad.sum(dim=(0, 2, 3), dtype=torch.float32)
+
+
+# how many times a bf16 tensor took each fused path since import (tests count them; nothing reads them on the hot path)
+LP_CALLS = {"bias_act": 0, "block_entry": 0, "down_entry": 0, "topdown_merge": 0, "stem_pool": 0}
+_LP = (torch.float32, torch.bfloat16)
+
+
+def _lp_ok(*tensors):
+    """The bf16 kernels' preconditions beyond the fp32 ones: channel count a multiple of 8, 16-byte aligned."""
+    return all(t.dtype != torch.bfloat16 or (t.shape[1] % 8 == 0 and not (t.data_ptr() & 15)) for t in tensors if t is not None)
+
+
+def _cast_w(w, dtype):
+    """The (folded) weight in the activation's dtype: a cast inside the graph, so its gradient arrives in fp32."""
+    return w if w.dtype == dtype else w.to(dtype)
 
 
 def bias_act(x, bias, residual=None, relu=True):
     """act(x + bias[:, None, None] (+ residual)); fused and in place for channels-last fp32 CUDA tensors
     fresh out of a convolution, plain torch ops otherwise."""
-    fast = (FUSE_EPILOGUE and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] > 1
+    fast = (FUSE_EPILOGUE and x.is_cuda and x.dtype in _LP and x.dim() == 4 and x.shape[1] > 1
             and x.is_contiguous(memory_format=torch.channels_last) and bias.dtype == torch.float32
-            and (residual is None or (residual.shape == x.shape and residual.dtype == torch.float32
-                                      and residual.is_contiguous(memory_format=torch.channels_last))))
+            and (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype
+                                      and residual.is_contiguous(memory_format=torch.channels_last)))
+            and _lp_ok(x, residual))
     if fast:
         state = {} if relu else None
         y = _BiasAct.apply(x, bias.contiguous(), residual, relu, state)
         if state:                       # the sign mask exists: a _BlockEntry consuming y may take over the ReLU backward
             y._dib_relu_state = state
         return y
-    y = x + bias.reshape(1, -1, 1, 1)
+    y = x + bias.reshape(1, -1, 1, 1)      # a bf16 x is promoted to fp32 here: same arithmetic as the kernel, one rounding below
     if residual is not None:
         y = y + residual
+    if x.dtype == torch.bfloat16 and y.dtype != x.dtype:
+        # rounded BEFORE the ReLU (same values: rounding keeps the sign), so that the ReLU's backward looks at the STORED value as
+        # the kernel's sign mask does -- a positive fp32 sum below bf16's smallest denormal is stored as zero and gets no gradient
+        y = y.to(x.dtype)
     return F.relu(y) if relu else y
 
 
@@ -142,6 +174,11 @@ def _as_gemm(x, conv, forward_only=False):
             and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
         return False
     M = x.shape[0] * x.shape[2] * x.shape[3]
+    if x.dtype == torch.bfloat16:
+        # bf16 (profiles/amp_trunk.txt): measured at b = 1 without autograd only.  There MIOpen's bf16 channels-last kernels differ
+        # from run to run on every 1x1 shape with M <= 16,800, which a replayed graph must not, and the GEMM is as fast or faster on
+        # all of the trunk's 1x1 shapes (24-110 us -> 22-29 us).  Training shapes are not measured: off under autograd.
+        return not forward_only and not torch.is_grad_enabled() and M <= 67200
     if M <= 16384 and conv.in_channels * conv.out_channels >= 512 * 1024:
         return True
     # forward alone (the entry nodes' forward pass; inference): the GEMM also wins at M <= 67,200 unless both channel
@@ -162,6 +199,24 @@ def _as_strided_gemm(x, conv):
             and x.is_contiguous(memory_format=torch.channels_last) and max(conv.in_channels, conv.out_channels) >= 128)
 
 
+# bf16 inference only: every 3x3 convolution with M <= 16,800 output pixels as im2col + GEMM (hipBLASLt).  Without find-db records
+# for bf16, MIOpen ranks its solvers by a search of its own in every process; for these small-M shapes the winner is in some
+# processes a split-K kernel that accumulates with atomics -- channels-last AND planar, stride 1 and 2 (seen in one process of
+# three for the planar kernels): two runs differ in the last bits (profiles/amp_trunk.txt), which a replayed graph must not.  The
+# larger shapes (M = 67,200 at b = 1) stayed bit-identical in MIOpen's channels-last kernels in every process.  The column buffers
+# are at most 77 MB at b = 1.
+SMALL_M_3X3_GEMM = True
+
+
+def _as_unfold_gemm(x, conv):
+    if not (SMALL_M_3X3_GEMM and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+            and conv.kernel_size == (3, 3) and conv.stride[0] == conv.stride[1] and conv.dilation == (1, 1) and conv.groups == 1):
+        return False
+    ho = (x.shape[2] + 2 * conv.padding[0] - 3) // conv.stride[0] + 1
+    wo = (x.shape[3] + 2 * conv.padding[1] - 3) // conv.stride[1] + 1
+    return x.shape[0] * ho * wo <= 16800
+
+
 # MIOpen's channels-last fp32 kernels are the fast ones for the large activations of this network; for the small-M, wide 3x3
 # convolutions of ResNet layer4 (512 -> 512 at 25 x 42: M = 8,400 at b = 8) its planar kernels are 2.2x faster forward and 1.4x
 # backward (scratch/t_conv3x3_layout.py: 0.91 / 0.57 ms -> 0.41 / 0.41 ms), far more than the two 17 MB layout changes cost.
@@ -174,6 +229,11 @@ def _as_planar(x, conv):
         return False
     ho = (x.shape[2] + 2 * conv.padding[0] - 3) // conv.stride[0] + 1
     wo = (x.shape[3] + 2 * conv.padding[1] - 3) // conv.stride[1] + 1
+    if x.dtype == torch.bfloat16:
+        # bf16 (profiles/amp_trunk.txt): off.  The planar kernels win at M = 16,800 without autograd (162 -> 75 us), but which solver
+        # MIOpen picks for them differs from process to process and some are not bit-reproducible: inference takes _as_unfold_gemm
+        # for those shapes; training shapes are not measured.
+        return False
     if conv.in_channels >= 512 and x.shape[0] * ho * wo <= 16384:
         return True
     # inference: at batch 1 the planar kernels win from 128 channels on wherever M <= 16,800 (256 -> 256 at 50 x 84:
@@ -237,6 +297,15 @@ def conv1x1(x, weight, bias, conv):
         s = conv.stride[0]
         xs = x[:, :, ::s, ::s].contiguous(memory_format=torch.channels_last)
         return F.linear(xs.permute(0, 2, 3, 1), weight.reshape(conv.out_channels, conv.in_channels), bias).permute(0, 3, 1, 2)
+    if _as_unfold_gemm(x, conv):
+        N, _, H, W = x.shape
+        ho = (H + 2 * conv.padding[0] - 3) // conv.stride[0] + 1
+        wo = (W + 2 * conv.padding[1] - 3) // conv.stride[1] + 1
+        cols = F.unfold(x, 3, padding=conv.padding, stride=conv.stride)                      # [N, Cin * 9, ho * wo], (c, kh, kw) order
+        y = torch.matmul(weight.reshape(conv.out_channels, -1), cols).view(N, conv.out_channels, ho, wo)
+        if bias is not None:
+            y = y + bias.reshape(1, -1, 1, 1)
+        return y.contiguous(memory_format=torch.channels_last)
     if _as_planar(x, conv):
         y = F.conv2d(x.contiguous(), weight.contiguous(), bias, conv.stride, conv.padding, conv.dilation, conv.groups)
         return y.contiguous(memory_format=torch.channels_last)
@@ -279,6 +348,7 @@ class _BlockEntry(torch.autograd.Function):
         x, weight = ctx.saved_tensors[:2]
         mask = ctx.saved_tensors[2] if ctx.has_mask else None
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        lp = x.dtype == torch.bfloat16
         if not g_out.is_contiguous(memory_format=torch.channels_last):
             g_out = g_out.contiguous(memory_format=torch.channels_last)
         dx, dw, _ = torch.ops.aten.convolution_backward(g_out, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
@@ -289,11 +359,11 @@ class _BlockEntry(torch.autograd.Function):
             if g_skip is not None:
                 if not g_skip.is_contiguous(memory_format=torch.channels_last) or g_skip.data_ptr() & 15:
                     g_skip = g_skip.clone(memory_format=torch.channels_last)
-                _lib.check(_lib.lib().dib_add_relu_mask(dx.data_ptr(), g_skip.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                        dx.numel(), _lib.stream_of(dx)))
+                fn = _lib.lib().dib_add_relu_mask_bf16 if lp else _lib.lib().dib_add_relu_mask
+                _lib.check(fn(dx.data_ptr(), g_skip.data_ptr(), mask.data_ptr() if mask is not None else None, dx.numel(), _lib.stream_of(dx)))
             elif mask is not None:
-                _lib.check(_lib.lib().dib_relu_mask_backward(dx.data_ptr(), mask.data_ptr(), dx.data_ptr(), dx.numel(),
-                                                             _lib.stream_of(dx)))
+                fn = _lib.lib().dib_relu_mask_backward_bf16 if lp else _lib.lib().dib_relu_mask_backward
+                _lib.check(fn(dx.data_ptr(), mask.data_ptr(), dx.data_ptr(), dx.numel(), _lib.stream_of(dx)))
             if mask is not None:
                 # tell the producing _BiasAct which gradient tensor already carries its ReLU mask; it re-applies the mask (idempotent
                 # and linear, so always correct) to anything else -- e.g. the sum autograd forms when the output has a second consumer
@@ -330,11 +400,14 @@ class _DownEntry(torch.autograd.Function):
         if need_x:
             dx, dxs = cl(dx), cl(dxs)
             stream = _lib.stream_of(dx)
+            lp = dx.dtype == torch.bfloat16
             if ctx.s == 1:
-                _lib.check(_lib.lib().dib_add_relu_mask(dx.data_ptr(), dxs.data_ptr(), None, dx.numel(), stream))
+                fn = _lib.lib().dib_add_relu_mask_bf16 if lp else _lib.lib().dib_add_relu_mask
+                _lib.check(fn(dx.data_ptr(), dxs.data_ptr(), None, dx.numel(), stream))
             else:
                 N, C, H, W = dx.shape
-                _lib.check(_lib.lib().dib_scatter_add_nhwc(dx.data_ptr(), dxs.data_ptr(), N, H, W, dxs.shape[2], dxs.shape[3], C, ctx.s, stream))
+                fn = _lib.lib().dib_scatter_add_bf16_nhwc if lp else _lib.lib().dib_scatter_add_nhwc
+                _lib.check(fn(dx.data_ptr(), dxs.data_ptr(), N, H, W, dxs.shape[2], dxs.shape[3], C, ctx.s, stream))
         return (dx if need_x else None), (dw1 if need_w1 else None), (dwd if need_wd else None), None, None
 
 
@@ -441,13 +514,15 @@ def down_entry(x, conv1, bn1, convd, bnd):
             and conv1.bias is None and convd.bias is None and conv1.kernel_size == (1, 1) and conv1.stride == (1, 1)
             and convd.kernel_size == (1, 1) and convd.stride[0] == convd.stride[1] and convd.stride[0] in (1, 2)
             and conv1.padding == (0, 0) and convd.padding == (0, 0) and conv1.groups == 1 and convd.groups == 1
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0
+            and x.is_cuda and x.dtype in _LP and x.dim() == 4 and x.shape[1] % 4 == 0 and _lp_ok(x)
             and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15) and torch.is_grad_enabled()
             and x.requires_grad):
         return None
     w1, t1 = _train_fold(conv1, bn1)
     wd, td = _train_fold(convd, bnd)
-    a, d = _DownEntry.apply(x, w1, wd, conv1, convd)
+    if x.dtype == torch.bfloat16:
+        LP_CALLS["down_entry"] += 1
+    a, d = _DownEntry.apply(x, _cast_w(w1, x.dtype), _cast_w(wd, x.dtype), conv1, convd)
     return bias_act(a, t1, None, True), bias_act(d, td, None, False)
 
 
@@ -456,12 +531,14 @@ def block_entry(x, conv, bn):
     apply (CPU, planar tensors, odd channel counts, a batch-norm that is not frozen)."""
     if not (BLOCK_ENTRY and FUSE_EPILOGUE and FOLD_FROZEN_BN and isinstance(bn, FrozenBatchNorm2d) and conv.bias is None
             and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0
+            and x.is_cuda and x.dtype in _LP and x.dim() == 4 and x.shape[1] % 4 == 0 and _lp_ok(x)
             and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15) and torch.is_grad_enabled()
             and (x.requires_grad or conv.weight.requires_grad)):
         return None
     weight, shift = _train_fold(conv, bn)
-    out, skip = _BlockEntry.apply(x, weight, getattr(x, "_dib_relu_state", None), conv)
+    if x.dtype == torch.bfloat16:
+        LP_CALLS["block_entry"] += 1
+    out, skip = _BlockEntry.apply(x, _cast_w(weight, x.dtype), getattr(x, "_dib_relu_state", None), conv)
     return bias_act(out, shift, None, True), skip
 
 
@@ -470,11 +547,27 @@ def _fold_key(conv, bn):
             bn.running_var._version, bn.weight.data_ptr())
 
 
-def _folded(conv, bn):
+def _folded(conv, bn, dtype=torch.float32):
     """(weight * scale, shift) of a convolution + frozen batch-norm pair for inference, cached while neither changes (the fold
     is 5 tiny launches per convolution, ~1 ms of GPU time per image at batch 1, for values that never move).  The two result
     tensors are allocated ONCE per pair and from then on REWRITTEN IN PLACE when a weight or statistic changed: a HIP graph
-    captured over them (graphs.py) keeps valid pointers and reads current values once `refresh_folded` has run."""
+    captured over them (graphs.py) keeps valid pointers and reads current values once `refresh_folded` has run.
+    `dtype` other than fp32: the folded weight rounded once to that dtype, cached beside the fp32 fold under the same key and
+    rewritten in place with it (the shift stays fp32)."""
+    if dtype != torch.float32 and dtype != conv.weight.dtype:
+        weight, shift = _folded(conv, bn)
+        key = conv.__dict__["_dib_fold"][0]
+        hit = conv.__dict__.get("_dib_fold_lp")
+        if hit is None or hit[0] != key or hit[1].dtype != dtype:
+            with torch.no_grad():
+                if (hit is not None and hit[1].dtype == dtype and hit[1].shape == weight.shape and hit[1].stride() == weight.stride()
+                        and hit[1].device == weight.device):
+                    hit[1].copy_(weight)
+                    hit = (key, hit[1])
+                else:
+                    hit = (key, weight.to(dtype))
+            conv.__dict__["_dib_fold_lp"] = hit
+        return hit[1], shift
     key = _fold_key(conv, bn)
     hit = conv.__dict__.get("_dib_fold")
     if hit is None or hit[0] != key:
@@ -532,6 +625,8 @@ def refresh_folded(module):
             _folded(conv, bn)
             if "_dib_fold_planar" in conv.__dict__:
                 _folded_planar(conv, bn)
+            if "_dib_fold_lp" in conv.__dict__:
+                _folded(conv, bn, conv.__dict__["_dib_fold_lp"][1].dtype)
             n += 1
     module.__dict__["_dib_fold_state"] = (sum(t._version for t in watch), sum(1 for conv, _ in pairs if "_dib_fold" in conv.__dict__))
     return n
@@ -578,7 +673,7 @@ class _WideOut1x1(torch.autograd.Function):
 
 def _wide_out(x, conv):
     return (LINEAR_1X1 and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-            and conv.out_channels >= 1024 and conv.in_channels <= 256 and x.is_cuda and x.dim() == 4 and torch.is_grad_enabled()
+            and conv.out_channels >= 1024 and conv.in_channels <= 256 and x.is_cuda and x.dtype != torch.bfloat16 and x.dim() == 4 and torch.is_grad_enabled()
             and x.requires_grad and x.is_contiguous(memory_format=torch.channels_last)
             and 16384 < x.shape[0] * x.shape[2] * x.shape[3] <= 65536)
 
@@ -596,13 +691,21 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
     if FOLD_FROZEN_BN and isinstance(bn, FrozenBatchNorm2d) and conv.bias is None:
         if torch.is_grad_enabled() and conv.weight.requires_grad:
             weight, shift = _train_fold(conv, bn)
+            weight = _cast_w(weight, x.dtype)
         else:
-            weight, shift = _folded(conv, bn)
+            weight, shift = _folded(conv, bn, x.dtype)
         y = _WideOut1x1.apply(x, weight) if _wide_out(x, conv) else conv1x1(x, weight, None, conv)
         return bias_act(y, shift, residual, relu)
     if isinstance(bn, BatchNorm2d) and bn.mode_one:
         # the same convolution detours as the folded path (same MIOpen / hipBLASLt shapes), on the unfolded weight
         return bn.forward_fused_(conv1x1(x, conv.weight, conv.bias, conv), residual, relu)
+    if x.dtype != conv.weight.dtype:
+        # unfolded form on a reduced-precision activation: the convolution in x's dtype, the norm and the rest in fp32, one rounding
+        y = conv1x1(x, _cast_w(conv.weight, x.dtype), None if conv.bias is None else _cast_w(conv.bias, x.dtype), conv)
+        y = bn(y.float())
+        if residual is not None:
+            y = y + residual
+        return (F.relu(y) if relu else y).to(x.dtype)
     y = bn(conv(x))
     if residual is not None:
         y = y + residual
@@ -658,7 +761,7 @@ class Bottleneck(nn.Module):
             idt = x if self.downsample is None else conv_bn(x, self.downsample[0], self.downsample[1])
             mid = None
             if (PLANAR_FUSED and not torch.is_grad_enabled() and FOLD_FROZEN_BN and isinstance(self.bn1, FrozenBatchNorm2d)
-                    and self.conv1.bias is None and x.is_cuda):
+                    and self.conv1.bias is None and x.is_cuda and x.dtype != torch.bfloat16):
                 w1, t1 = _folded(self.conv1, self.bn1)
                 y1 = conv1x1(x, w1, None, self.conv1)
                 mid = _planar_middle(y1, t1, self.conv2, self.bn2)
@@ -678,14 +781,16 @@ class _StemPool(torch.autograd.Function):
     element (dib_stem_pool_backward) -- ATen's max-pool backward and the ReLU backward in one."""
 
     @staticmethod
-    def forward(ctx, x, bias):
+    def forward(ctx, x, bias, out_dtype=torch.float32):
+        # x is the fp32 convolution output; out_dtype bf16: the pooled tensor is stored as bf16 (one rounding) and the backward
+        # pass reads a bf16 gradient -- the dense gradient it writes is the fp32 convolution's, fp32 either way
         from .. import _lib
         N, C, H, W = x.shape
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        out = torch.empty((N, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        out = torch.empty((N, C, Ho, Wo), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
         arg = torch.empty((N * Ho * Wo * (C // 4),), dtype=torch.int16, device=x.device)
-        _lib.check(_lib.lib().dib_stem_pool_forward(x.data_ptr(), bias.data_ptr(), out.data_ptr(), arg.data_ptr(), N, H, W, C,
-                                                    _lib.stream_of(x)))
+        fn = _lib.lib().dib_stem_pool_forward_bf16 if out_dtype == torch.bfloat16 else _lib.lib().dib_stem_pool_forward
+        _lib.check(fn(x.data_ptr(), bias.data_ptr(), out.data_ptr(), arg.data_ptr(), N, H, W, C, _lib.stream_of(x)))
         ctx.shape = (N, C, H, W)
         ctx.save_for_backward(arg)
         return out
@@ -697,14 +802,16 @@ class _StemPool(torch.autograd.Function):
         N, C, H, W = ctx.shape
         if not g.is_contiguous(memory_format=torch.channels_last) or (g.data_ptr() & 15):
             g = g.clone(memory_format=torch.channels_last)
-        gx = torch.empty((N, C, H, W), dtype=g.dtype, device=g.device, memory_format=torch.channels_last)
-        _lib.check(_lib.lib().dib_stem_pool_backward(g.data_ptr(), arg.data_ptr(), gx.data_ptr(), N, H, W, C,
-                                                     _lib.stream_of(g)))
-        return gx, (gx.sum(dim=(0, 2, 3)) if ctx.needs_input_grad[1] else None)
+        gx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
+        fn = _lib.lib().dib_stem_pool_backward_bf16 if g.dtype == torch.bfloat16 else _lib.lib().dib_stem_pool_backward
+        _lib.check(fn(g.data_ptr(), arg.data_ptr(), gx.data_ptr(), N, H, W, C, _lib.stream_of(g)))
+        return gx, (gx.sum(dim=(0, 2, 3)) if ctx.needs_input_grad[1] else None), None
 
 
-def stem(x, conv, bn):
-    """max_pool2d(relu(bn(conv(x))), 3, stride=2, padding=1): the ResNet stem."""
+def stem(x, conv, bn, out_dtype=None):
+    """max_pool2d(relu(bn(conv(x))), 3, stride=2, padding=1): the ResNet stem.  `out_dtype` (bf16 under --amp): the 7x7
+    convolution of the 3-channel image and its epilogue run in fp32 as always, only the pooled result is stored in out_dtype."""
+    lp = out_dtype is not None and out_dtype != x.dtype
     if (FUSE_STEM_POOL and FUSE_EPILOGUE and FOLD_FROZEN_BN and isinstance(bn, FrozenBatchNorm2d) and conv.bias is None and x.is_cuda
             and x.dtype == torch.float32 and conv.out_channels % 4 == 0):
         if torch.is_grad_enabled() and conv.weight.requires_grad:
@@ -713,9 +820,15 @@ def stem(x, conv, bn):
             weight, shift = _folded(conv, bn)
         y = conv1x1(x, weight, None, conv)
         if y.is_contiguous(memory_format=torch.channels_last) and not (y.data_ptr() & 15):
-            return _StemPool.apply(y, shift.contiguous())
-        return F.max_pool2d(bias_act(y, shift, None, True), 3, stride=2, padding=1)
-    return F.max_pool2d(conv_bn(x, conv, bn, relu=True), 3, stride=2, padding=1)
+            if lp and out_dtype == torch.bfloat16:
+                LP_CALLS["stem_pool"] += 1
+                return _StemPool.apply(y, shift.contiguous(), out_dtype)
+            y = _StemPool.apply(y, shift.contiguous(), torch.float32)
+            return y.to(out_dtype) if lp else y
+        y = F.max_pool2d(bias_act(y, shift, None, True), 3, stride=2, padding=1)
+        return y.to(out_dtype) if lp else y
+    y = F.max_pool2d(conv_bn(x, conv, bn, relu=True), 3, stride=2, padding=1)
+    return y.to(out_dtype) if lp else y
 
 
 class ResNet50Body(nn.Module):
@@ -739,10 +852,10 @@ class ResNet50Body(nn.Module):
         layers += [Bottleneck(self.inplanes, planes, norm_layer=norm_layer) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
-    def forward(self, x):
+    def forward(self, x, compute_dtype=None):
         parked = _begin_step_folds(self, x)
         try:
-            x = stem(x, self.conv1, self.bn1)
+            x = stem(x, self.conv1, self.bn1, compute_dtype)
             c2 = self.layer1(x)
             c3 = self.layer2(c2)
             c4 = self.layer3(c3)
@@ -767,14 +880,14 @@ class _TopDownMerge(torch.autograd.Function):
         N, C, H, W = x.shape
         ctx.top_shape = tuple(top.shape)
         ctx.mark_dirty(x)
-        _lib.check(_lib.lib().dib_fpn_topdown_merge_nhwc(x.data_ptr(), bias.data_ptr(), top.data_ptr(), N, H, W, top.shape[2], top.shape[3], C,
-                                                         _lib.stream_of(x)))
+        fn = _lib.lib().dib_fpn_topdown_merge_bf16_nhwc if x.dtype == torch.bfloat16 else _lib.lib().dib_fpn_topdown_merge_nhwc
+        _lib.check(fn(x.data_ptr(), bias.data_ptr(), top.data_ptr(), N, H, W, top.shape[2], top.shape[3], C, _lib.stream_of(x)))
         return x
 
     @staticmethod
     def backward(ctx, g):
         need_x, need_b, need_t = ctx.needs_input_grad
-        g_b = g.sum((0, 2, 3)) if need_b else None
+        g_b = _channel_sum(g) if need_b else None
         g_t = None
         if need_t:
             g_t = torch.ops.aten.upsample_nearest2d_backward(g, list(g.shape[-2:]), list(ctx.top_shape), None, None)
@@ -784,11 +897,14 @@ class _TopDownMerge(torch.autograd.Function):
 def topdown_merge(lateral, bias, top):
     """lateral (a convolution output WITHOUT its bias) + bias + nearest-upsampled `top`."""
     cl = lambda t: t.is_contiguous(memory_format=torch.channels_last) and not (t.data_ptr() & 15)   # noqa: E731
-    if (FUSE_TOPDOWN and FUSE_EPILOGUE and lateral.is_cuda and lateral.dtype == torch.float32 and top.dtype == torch.float32
+    if (FUSE_TOPDOWN and FUSE_EPILOGUE and lateral.is_cuda and lateral.dtype in _LP and top.dtype == lateral.dtype
             and lateral.dim() == 4 and lateral.shape[1] % 4 == 0 and lateral.shape[:2] == top.shape[:2] and cl(lateral) and cl(top)
-            and bias.dtype == torch.float32):
+            and bias.dtype == torch.float32 and _lp_ok(lateral)):
+        if lateral.dtype == torch.bfloat16:
+            LP_CALLS["topdown_merge"] += 1
         return _TopDownMerge.apply(lateral, bias.contiguous(), top)
-    return lateral + bias.reshape(1, -1, 1, 1) + F.interpolate(top, size=lateral.shape[-2:], mode="nearest")
+    y = lateral + bias.reshape(1, -1, 1, 1) + F.interpolate(top, size=lateral.shape[-2:], mode="nearest")
+    return y.to(lateral.dtype) if lateral.dtype == torch.bfloat16 and y.dtype != lateral.dtype else y      # bf16: summed in fp32 (the bias promotes), one rounding
 
 
 class FeaturePyramidNetwork(nn.Module):
@@ -804,6 +920,8 @@ class FeaturePyramidNetwork(nn.Module):
                 nn.init.constant_(conv.bias, 0)
 
     def forward(self, feats):
+        if feats[0].dtype != self.inner_blocks[0].weight.dtype:
+            return self._forward_lp(feats)
         lat = lambda i: conv1x1(feats[i], self.inner_blocks[i].weight, self.inner_blocks[i].bias, self.inner_blocks[i])  # noqa: E731
         last = lat(-1)
         out = lambda i, t: conv1x1(t, self.layer_blocks[i].weight, self.layer_blocks[i].bias, self.layer_blocks[i])  # noqa: E731
@@ -811,6 +929,21 @@ class FeaturePyramidNetwork(nn.Module):
         for i in range(len(feats) - 2, -1, -1):
             blk = self.inner_blocks[i]
             last = topdown_merge(conv1x1(feats[i], blk.weight, None, blk), blk.bias, last)
+            outs.insert(0, out(i, last))
+        outs.append(F.max_pool2d(outs[-1], 1, 2, 0))
+        return OrderedDict(zip(["0", "1", "2", "3", "pool"], outs))
+
+    def _forward_lp(self, feats):
+        """The same pathway on reduced-precision (bf16) features: every convolution with a copy of its fp32 weight cast inside
+        the graph, every bias as an fp32 vector in the epilogue behind it (bias_act / topdown_merge: one rounding per store)."""
+        dt = feats[0].dtype
+        conv = lambda t, blk: conv1x1(t, _cast_w(blk.weight, dt), None, blk)  # noqa: E731
+        out = lambda i, t: bias_act(conv(t, self.layer_blocks[i]), self.layer_blocks[i].bias, relu=False)  # noqa: E731
+        last = bias_act(conv(feats[-1], self.inner_blocks[-1]), self.inner_blocks[-1].bias, relu=False)
+        outs = [out(-1, last)]
+        for i in range(len(feats) - 2, -1, -1):
+            blk = self.inner_blocks[i]
+            last = topdown_merge(conv(feats[i], blk), blk.bias, last)
             outs.insert(0, out(i, last))
         outs.append(F.max_pool2d(outs[-1], 1, 2, 0))
         return OrderedDict(zip(["0", "1", "2", "3", "pool"], outs))
@@ -827,9 +960,20 @@ class BackboneWithFPN(nn.Module):
                 p.requires_grad_(False)
         self.fpn = FeaturePyramidNetwork([256, 512, 1024, 2048], out_channels)
         self.out_channels = out_channels
+        # torch.bfloat16 (`--amp`): activations and matrix math of body + FPN in bf16 behind the fp32 stem convolution; parameters,
+        # buffers and their gradients stay fp32.  A plain attribute: not part of the state dict.
+        self.compute_dtype = torch.float32
 
     def forward(self, x):
-        return self.fpn(self.body(x))
+        if self.compute_dtype == torch.float32 or x.dtype != torch.float32:
+            return self.fpn(self.body(x))
+        lp = self.fpn(self.body(x, self.compute_dtype))
+        out = OrderedDict()
+        for k, v in lp.items():
+            # fp32 for RoIAlign, the warper and the heads; the RPN head reads the level it was upcast from (no second conversion)
+            out[k] = v.float()
+            out[k]._dib_lp = v
+        return out
 
 
 def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_layers=3):

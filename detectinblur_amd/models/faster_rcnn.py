@@ -79,10 +79,13 @@ def find_pretrained(kind):
 
 
 def fasterrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True,
-                            trainable_backbone_layers=3, channels_last=True, **kwargs):
+                            trainable_backbone_layers=3, channels_last=True, compute_dtype=torch.float32, **kwargs):
     """reference models/faster_rcnn.py:301-373.  `pretrained_backbone="auto"`: ImageNet trunk if a cached
     file exists, random initialisation (with a note) otherwise -- what `train.py` asks for, since the
-    reference's default (True) means "download"."""
+    reference's default (True) means "download".  `compute_dtype=torch.bfloat16` (this repo, `--amp`): bf16 activations and
+    matrix math in the trunk and the RPN head's 3x3 convolution, fp32 parameters (models/backbone.py: BackboneWithFPN)."""
+    if compute_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16, got %s" % (compute_dtype,))
     assert 0 <= trainable_backbone_layers <= 5
     full = find_pretrained("fasterrcnn_resnet50_fpn_coco") if pretrained else None
     if pretrained and full is None:
@@ -113,6 +116,7 @@ def fasterrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pre
         if missing or unexpected:
             raise RuntimeError("%s does not hold a torchvision ResNet-50 state dict: missing %s, unexpected %s"
                                % (trunk, missing[:5], unexpected[:5]))
+    backbone.compute_dtype = compute_dtype
     model = FasterRCNN(backbone, num_classes, **kwargs)
     if full is not None:
         model.load_state_dict(torch.load(full, map_location="cpu", weights_only=True))

@@ -70,27 +70,35 @@ class RPNHead(nn.Module):
         is read once forward, and its gradient comes out of one data-gradient kernel instead of two plus autograd's add."""
         logits, deltas = [], []
         A = self.cls_logits.out_channels
-        fused = FUSE_HEAD and feats and feats[0].is_cuda
+        # a bf16 trunk (BackboneWithFPN.compute_dtype) leaves each fp32 level with the bf16 tensor it was upcast from: the head
+        # reads that one -- 3x3 convolution, epilogue and the predictors' contraction in bf16, logits and deltas upcast to fp32
+        feats = [getattr(f, "_dib_lp", f) for f in feats]
+        lp = bool(feats) and feats[0].dtype != self.conv.weight.dtype
+        fused = (FUSE_HEAD and feats and feats[0].is_cuda) or lp
         if fused:
             # padded to a multiple of 4 output channels: ATen's channels-last bias-gradient reduction takes 0.69 ms for 15
             # channels at 200 x 336 and 0.02 ms for 12 or 16 (scratch/t_bias_grad.py)
             pad = (-5 * A) % 4
             w = torch.cat([self.cls_logits.weight, self.bbox_pred.weight] + ([self.conv.weight.new_zeros((pad,) + tuple(self.cls_logits.weight.shape[1:]))] if pad else []))
             b = torch.cat([self.cls_logits.bias, self.bbox_pred.bias] + ([self.conv.bias.new_zeros(pad)] if pad else []))
+            if lp:
+                w, b, cw = w.to(feats[0].dtype), b.to(feats[0].dtype), self.conv.weight.to(feats[0].dtype)
         for f in feats:
             if not fused:
                 t = F.relu(conv1x1(f, self.conv.weight, self.conv.bias, self.conv))
                 logits.append(self.cls_logits(t))
                 deltas.append(self.bbox_pred(t))
                 continue
-            t = bias_act(conv1x1(f, self.conv.weight, None, self.conv), self.conv.bias, relu=True)   # shape-based kernel choice
-            if torch.is_grad_enabled():
+            t = bias_act(conv1x1(f, cw if lp else self.conv.weight, None, self.conv), self.conv.bias, relu=True)   # shape-based kernel choice
+            if torch.is_grad_enabled() or not f.is_cuda:
                 both = F.conv2d(t, w, b)
             else:
                 # inference: the same contraction as a GEMM on the NHWC view.  MIOpen's kernel for this 1 x 1 convolution with 16
                 # output channels accumulates with atomics at every level but the largest: two runs on the same input differ in
                 # the last bits, and with them the proposals (scratch/t_pred_conv.py: 20 of 20 runs differ; the GEMM: 0, same time)
                 both = F.linear(t.permute(0, 2, 3, 1), w.view(w.shape[0], -1), b).permute(0, 3, 1, 2)
+            if lp:
+                both = both.float()
             logits.append(both[:, :A])
             deltas.append(both[:, A:5 * A])
         return logits, deltas

@@ -70,6 +70,9 @@ def reject_out_of_scope(args):
     for name, what in _OUT_OF_SCOPE.items():
         if getattr(args, name, False):
             raise SystemExit("--%s: %s is outside the built hot path (SURVEY.md section 2)" % (name, what))
+    if getattr(args, "amp", False) and getattr(args, "mode_one_norm", False):
+        raise SystemExit("--amp with --mode_one_norm: the test-time batch-norm kernel (dib_bn_mode_one_nhwc) and its tolerances are fp32; "
+                         "drop one of the two flags")
     if "coco" not in args.dataset:
         raise SystemExit("--dataset %s: only COCO (and --synthetic) is built; real-blur datasets are outside the hot path" % args.dataset)
     if "fasterrcnn_resnet50_fpn" not in args.model:
@@ -122,14 +125,20 @@ def add_shared_flags(p):
     p.add_argument("--aug_mix_target_expand", action="store_true",
                    help="Expand target boxes for AugMix according to positional shifts from spatial augmentations.")
     p.add_argument("--unfrozen_batch_norm", action="store_true", help="(not built)")
+    p.add_argument("--amp", action="store_true", help="(this repo) bfloat16 activations and matrix math "
+                   "in the ResNet-50 body, the FPN and the RPN head's 3x3 convolution; fp32 master weights, gradients, optimizer, heads, losses")
     p.add_argument("--world-size", default=1, type=int, help="number of distributed processes")
     p.add_argument("--dist-url", default="env://", help="url used to set up distributed training")
     return p
 
 
 def detector_size_kwargs(args):
-    """--min_size / --max_size as FasterRCNN keyword arguments (absent: the reference's 800 / 1333)."""
-    return {k: getattr(args, k) for k in ("min_size", "max_size") if getattr(args, k, None) is not None}
+    """--min_size / --max_size as FasterRCNN keyword arguments (absent: the reference's 800 / 1333), and --amp as the trunk's
+    compute_dtype."""
+    kw = {k: getattr(args, k) for k in ("min_size", "max_size") if getattr(args, k, None) is not None}
+    if getattr(args, "amp", False):
+        kw["compute_dtype"] = torch.bfloat16
+    return kw
 
 
 def build_parser():

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
+#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes, the bf16 epilogues dib_bias_act_bf16_nhwc, dib_bias_act_mask_bf16_nhwc, dib_relu_mask_backward_bf16, dib_add_relu_mask_bf16, dib_scatter_add_bf16_nhwc, dib_fpn_topdown_merge_bf16_nhwc, dib_stem_pool_forward_bf16 / _backward_bf16): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
                              per-tap offset array (sizes come from dib_tap_table_bytes as before)          */
 
 /* error codes */
@@ -389,6 +389,32 @@ int dib_stem_pool_forward(const float *x_dev, const float *bias_dev, float *out_
                           void *stream);
 int dib_stem_pool_backward(const float *grad_out_dev, const unsigned short *arg_dev, float *grad_in_dev, int N, int H, int W, int C,
                            void *stream);
+
+/* bfloat16 forms of the epilogues above (the trunk under `--amp`, models/backbone.py): activations, residuals and gradients are
+ * channels-last bf16 (raw 16-bit words), bias vectors stay fp32.  Each upcasts, runs the fp32 kernel's arithmetic in its order
+ * and rounds once to nearest even at the store (NaN stays NaN, +-inf stays): bit-identical to the torch expression evaluated in
+ * fp32 and cast once.  8 elements per lane: C % 8 == 0 (n_elems % 8 == 0), 16-byte aligned tensors, no scalar variant.
+ *   dib_bias_act_bf16_nhwc / _mask_:  x = bf16(act(float(x) + bias[c] (+ float(residual)))) in place; mask_dev[n_elems / 8], one byte
+ *       per 8 consecutive elements, bit k = STORED element 8 i + k is > 0
+ *   dib_relu_mask_backward_bf16:      grad_out = mask ? grad_in : +0 (may alias)
+ *   dib_add_relu_mask_bf16:           a = bf16(float(a) + float(b)), then zeroed where the mask bit is clear (mask_dev NULL: plain add)
+ *   dib_scatter_add_bf16_nhwc:        a[n, ys * stride, xs * stride, :] = bf16(float(a) + float(b[n, ys, xs, :]))
+ *   dib_fpn_topdown_merge_bf16_nhwc:  x = bf16((float(x) + bias) + float(top at ATen's nearest source pixel)) in place
+ *   dib_stem_pool_forward_bf16:       the stem's 7x7 convolution stays fp32 (3 input channels): x_dev fp32, out_dev bf16 =
+ *       bf16(max_pool2d(relu(x + bias))), window order, tie rule and arg_dev exactly as dib_stem_pool_forward (C % 4 == 0)
+ *   dib_stem_pool_backward_bf16:      grad_out_dev bf16 + arg -> grad_in_dev fp32 (summed in fp32 in dib_stem_pool_backward's order) */
+int dib_bias_act_bf16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C, int relu, void *stream);
+int dib_bias_act_mask_bf16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C,
+                                unsigned char *mask_dev, void *stream);
+int dib_relu_mask_backward_bf16(const void *grad_in_dev, const unsigned char *mask_dev, void *grad_out_dev, long long n_elems, void *stream);
+int dib_add_relu_mask_bf16(void *a_dev, const void *b_dev, const unsigned char *mask_dev, long long n_elems, void *stream);
+int dib_scatter_add_bf16_nhwc(void *a_dev, const void *b_dev, int N, int H, int W, int Hs, int Ws, int C, int stride, void *stream);
+int dib_fpn_topdown_merge_bf16_nhwc(void *x_dev, const float *bias_dev, const void *top_dev, int N, int H, int W, int Ht, int Wt, int C,
+                                    void *stream);
+int dib_stem_pool_forward_bf16(const float *x_dev, const float *bias_dev, void *out_dev, unsigned short *arg_dev, int N, int H, int W, int C,
+                               void *stream);
+int dib_stem_pool_backward_bf16(const void *grad_out_dev, const unsigned short *arg_dev, float *grad_in_dev, int N, int H, int W, int C,
+                                void *stream);
 
 /* Frozen batch-norm folds of n trunk convolutions in one launch per 32 (torchvision's FrozenBatchNorm2d behind every ResNet
  * convolution, reference models/faster_rcnn.py:367; training re-folds every step because the weights move):
