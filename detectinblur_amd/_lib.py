@@ -129,21 +129,6 @@ _SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "dib_stem_pool_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_void_p]),
-    # bf16 forms (same argument lists as the fp32 entries above)
-    "dib_bias_act_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_void_p]),
-    "dib_bias_act_mask_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
-                                                   ctypes.c_void_p, ctypes.c_void_p]),
-    "dib_relu_mask_backward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
-    "dib_add_relu_mask_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
-    "dib_scatter_add_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "dib_fpn_topdown_merge_bf16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "dib_stem_pool_forward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "dib_stem_pool_backward_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_void_p]),
     "dib_fold_bn_multi": (ctypes.c_int, [_c_void_pp, _c_void_pp, _c_void_pp, _c_void_pp, _c_void_pp, _c_int_p, _c_int_p, ctypes.c_int,
                                          ctypes.c_float, _c_void_pp, _c_void_pp, _c_void_pp, ctypes.c_void_p]),
     "dib_scale_rows_multi": (ctypes.c_int, [_c_void_pp, _c_void_pp, _c_int_p, _c_int_p, ctypes.c_int, _c_void_pp, ctypes.c_void_p]),
@@ -164,6 +149,15 @@ _SIGNATURES = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.c_void_p]),
 }
+
+# The trunk's epilogue family (csrc/dib_eltwise_vec.h): an fp32 and a bf16 entry point per member, with one argument list.  LANE:
+# elements per 16-byte lane vector by activation dtype (channel and element counts are multiples of it, one sign-mask byte each).
+LANE = {torch.float32: 4, torch.bfloat16: 8}
+_FAMILY = {"bias_act": "dib_bias_act%s_nhwc", "bias_act_mask": "dib_bias_act_mask%s_nhwc", "relu_mask_backward": "dib_relu_mask_backward%s",
+           "add_relu_mask": "dib_add_relu_mask%s", "scatter_add": "dib_scatter_add%s_nhwc", "topdown_merge": "dib_fpn_topdown_merge%s_nhwc",
+           "stem_pool_forward": "dib_stem_pool_forward%s", "stem_pool_backward": "dib_stem_pool_backward%s"}
+_SIGNATURES.update({pattern % "_bf16": _SIGNATURES[pattern % ""] for pattern in _FAMILY.values()})
+_family = {}      # (member, dtype) -> entry point, resolved once: the lookup sits on every launch's host path
 
 EXPORTS = tuple(k for k in _SIGNATURES if k != "dib_sparse_blur_generic")
 
@@ -194,6 +188,13 @@ def lib():
             raise ImportError("libdib_hip.so ABI version mismatch")
         _lib = l
     return _lib
+
+
+def family(member, dtype):
+    """The entry point of a member of the epilogue family (a key of _FAMILY) for activations of `dtype`; KeyError for any other dtype."""
+    if not _family:
+        _family.update({(m, dt): getattr(lib(), p % sfx) for m, p in _FAMILY.items() for dt, sfx in ((torch.float32, ""), (torch.bfloat16, "_bf16"))})
+    return _family[member, dtype]
 
 
 def check(code):

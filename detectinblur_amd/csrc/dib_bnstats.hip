@@ -12,7 +12,7 @@
 //      per slice goes to the workspace.
 //   2. bn_finalize_kernel: 64 channels per workgroup, 16 lanes per channel merge the slices (lane j: slices j, j + 16, ...,
 //      in order), the 16 partial results merge in lane order; then the mix above and scale / shift.
-//   3. bn_apply_kernel: the in-place pass of bias_act_vec4_kernel (dib_eltwise.hip) with a scale.
+//   3. bn_apply_kernel: the in-place pass of bias_act_kernel (dib_eltwise_vec.h) with a scale.
 // Every reduction runs in an order fixed by the shape alone: two calls on the same input are bitwise equal.
 #include "dib_common.h"
 

@@ -1,0 +1,388 @@
+// The trunk's epilogue family (detectinblur_amd/models/backbone.py), written once for both activation types: channels-last
+// (NHWC) activations stored as fp32 or as bf16, per-channel vectors (bias, folded shift) read as fp32.  A lane works on one
+// 16-byte vector: 4 fp32 in a float4 or 8 bf16 in a uint4 (every trunk width is a multiple of 64).  The bf16 form upcasts, does
+// the fp32 arithmetic in its order, and rounds ONCE (to nearest even) at the store, so each kernel is checkable bit for bit
+// against the torch expression evaluated in fp32 and cast once (tests/test_detector_ops.py, tests/test_amp_gpu.py).  Pure
+// streaming, HBM-bound; no atomics, no scratch.  dib_eltwise.hip instantiates the fp32 entry points, dib_eltwise_bf16.hip the
+// bf16 ones.
+#pragma once
+#include "dib_common.h"
+#include <initializer_list>
+
+namespace dib {
+
+// ---- the two lane vectors: what the kernels below do not share ---------------------------------------------------------------
+// N elements in a Raw; Quad = 4 pooled channels of the stem pool, whose convolution side is fp32 in both forms.
+struct F32Lane {
+  static constexpr int N = 4;
+  static constexpr bool TOP_BEFORE_BIAS = false;      // topdown_merge_kernel
+  typedef float4 Raw;
+  typedef float4 Quad;
+  static __device__ __forceinline__ void unpack(const Raw u, float v[N]) { v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; }
+  static __device__ __forceinline__ Raw pack(const float v[N]) { return make_float4(v[0], v[1], v[2], v[3]); }
+  static __device__ __forceinline__ float relu(float v) { return fmaxf(v, 0.f); }
+  // bit k = element k > 0
+  static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
+    return (u.x > 0.f ? 1 : 0) | (u.y > 0.f ? 2 : 0) | (u.z > 0.f ? 4 : 0) | (u.w > 0.f ? 8 : 0);
+  }
+  // mask ? element : 0 (torch's threshold_backward(grad, y, 0) with y > 0 read from the mask)
+  static __device__ __forceinline__ Raw select(Raw u, unsigned m) {
+    u.x = (m & 1u) ? u.x : 0.f; u.y = (m & 2u) ? u.y : 0.f; u.z = (m & 4u) ? u.z : 0.f; u.w = (m & 8u) ? u.w : 0.f;
+    return u;
+  }
+  static __device__ __forceinline__ Quad pack_quad(const float4 m) { return m; }
+  static __device__ __forceinline__ float quad(const Quad q, int k) { return k == 0 ? q.x : k == 1 ? q.y : k == 2 ? q.z : q.w; }
+};
+
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+struct Bf16Lane {
+  static constexpr int N = 8;
+  static constexpr bool TOP_BEFORE_BIAS = true;
+  typedef uint4 Raw;
+  typedef uint2 Quad;
+  static __device__ __forceinline__ float lo(unsigned u) { return __uint_as_float(u << 16); }
+  static __device__ __forceinline__ float hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+  // two fp32 -> two bf16 in one word, round to nearest even (v_cvt_pk_bf16_f32 on gfx950); NaN stays NaN, +-inf stays
+  static __device__ __forceinline__ unsigned pack2(float a, float b) {
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+  }
+  static __device__ __forceinline__ void unpack(const Raw u, float v[N]) {
+    v[0] = lo(u.x); v[1] = hi(u.x); v[2] = lo(u.y); v[3] = hi(u.y);
+    v[4] = lo(u.z); v[5] = hi(u.z); v[6] = lo(u.w); v[7] = hi(u.w);
+  }
+  static __device__ __forceinline__ Raw pack(const float v[N]) {
+    return make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+  }
+  // torch's relu (clamp_min): a NaN goes through
+  static __device__ __forceinline__ float relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
+  // bit k = STORED element k > 0 (the value AFTER rounding: a positive fp32 below half of bf16's smallest denormal is stored
+  // as zero and gets no gradient, as in the plain graph on the stored tensor)
+  static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
+    float v[N];
+    unpack(u, v);
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) m |= (v[k] > 0.f ? 1u : 0u) << k;
+    return m;
+  }
+  // keep the halves of the four words whose mask bit is set (cleared ones become +0, torch's threshold_backward)
+  static __device__ __forceinline__ Raw select(const Raw u, unsigned m) {
+    auto keep = [](unsigned w, unsigned b) { return w & (((b & 1u) ? 0xffffu : 0u) | ((b & 2u) ? 0xffff0000u : 0u)); };
+    return make_uint4(keep(u.x, m), keep(u.y, m >> 2), keep(u.z, m >> 4), keep(u.w, m >> 6));
+  }
+  static __device__ __forceinline__ Quad pack_quad(const float4 m) { return make_uint2(pack2(m.x, m.y), pack2(m.z, m.w)); }
+  static __device__ __forceinline__ float quad(const Quad q, int k) { return (k & 1) ? hi(k < 2 ? q.x : q.y) : lo(k < 2 ? q.x : q.y); }
+};
+
+template <class L>
+__device__ __forceinline__ void add(float v[L::N], const float w[L::N]) {
+#pragma unroll
+  for (int k = 0; k < L::N; ++k) v[k] += w[k];
+}
+// v += bias[c * N .. c * N + N) for the lane's vector index c within a pixel
+template <class L>
+__device__ __forceinline__ void add_bias(float v[L::N], const float4 *__restrict__ bias, int c) {
+#pragma unroll
+  for (int k = 0; k < L::N / 4; ++k) {
+    const float4 b = bias[c * (L::N / 4) + k];
+    v[4 * k] += b.x; v[4 * k + 1] += b.y; v[4 * k + 2] += b.z; v[4 * k + 3] += b.w;
+  }
+}
+
+// ---- kernels -------------------------------------------------------------------------------------------------------------------
+// Fused per-channel bias + residual + ReLU, the epilogue of every convolution of the ResNet-50 trunk once its frozen batch-norm
+// is folded into the weights: x = act(x + bias[c] (+ res)) in place on the convolution output.  Stock eager PyTorch runs it as
+// 2-4 full passes over the activation (bias add, residual add, ReLU); here it is one pass (fp32: 8 bytes per element without
+// a residual, 12 with one).
+// MASK: also write the ReLU's sign pattern, one byte per vector: what the backward pass needs of the output, at 1/16 of its
+// size (the fp32 backward then reads 4.25 instead of 8 bytes per element).
+template <class L, bool RES, bool RELU, bool MASK>
+__global__ __launch_bounds__(256) void bias_act_kernel(typename L::Raw *__restrict__ x, const float4 *__restrict__ bias,
+                                                      const typename L::Raw *__restrict__ res, long long n, int CV,
+                                                      unsigned char *__restrict__ mask) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    float v[L::N];
+    L::unpack(x[i], v);
+    add_bias<L>(v, bias, (int)(i % CV));
+    if (RES) {
+      float r[L::N];
+      L::unpack(res[i], r);
+      add<L>(v, r);
+    }
+    if (RELU) {
+#pragma unroll
+      for (int k = 0; k < L::N; ++k) v[k] = L::relu(v[k]);
+    }
+    const typename L::Raw o = L::pack(v);
+    x[i] = o;
+    if (MASK) mask[i] = (unsigned char)L::sign_mask(o);
+  }
+}
+
+// ReLU backward from that mask: out = mask ? grad : 0.
+template <class L>
+__global__ __launch_bounds__(256) void relu_mask_bwd_kernel(const typename L::Raw *__restrict__ g, const unsigned char *__restrict__ mask,
+                                                           typename L::Raw *__restrict__ out, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    out[i] = L::select(g[i], mask[i]);
+}
+
+// Gradient accumulation at a residual block's input fused with the ReLU backward of the tensor it belongs to:
+// a = (a + b) [masked], one pass (fp32: 12.25 B per element) where autograd's add followed by a mask pass moves 20.25.
+template <class L, bool MASK>
+__global__ __launch_bounds__(256) void add_mask_kernel(typename L::Raw *__restrict__ a, const typename L::Raw *__restrict__ b,
+                                                      const unsigned char *__restrict__ mask, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    float v[L::N], w[L::N];
+    L::unpack(a[i], v);
+    L::unpack(b[i], w);
+    add<L>(v, w);
+    typename L::Raw o = L::pack(v);
+    if (MASK) o = L::select(o, mask[i]);
+    a[i] = o;
+  }
+}
+
+// Data gradient of a strided 1x1 convolution added into the data gradient of the stride-1 convolution that shares its input
+// (the downsample path of a ResNet stage's first block): a[n, ys * s, xs * s, :] += b[n, ys, xs, :], channels-last, in place.
+// Replaces a zero-filled full-size gradient plus a full-size add by a pass over a quarter of the pixels.
+template <class L>
+__global__ __launch_bounds__(256) void scatter_add_kernel(typename L::Raw *__restrict__ a, const typename L::Raw *__restrict__ b, int Hs,
+                                                         int Ws, int CV, int H, int W, int s, long long n_vec) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % CV);
+    long long p = i / CV;
+    const int xs = (int)(p % Ws);
+    p /= Ws;
+    const int ys = (int)(p % Hs);
+    const long long n = p / Hs;
+    const long long j = ((n * H + (long long)ys * s) * W + (long long)xs * s) * CV + c;
+    float v[L::N], w[L::N];
+    L::unpack(a[j], v);
+    L::unpack(b[i], w);
+    add<L>(v, w);
+    a[j] = L::pack(v);
+  }
+}
+
+// FPN top-down merge in one pass, in place on the lateral convolution's output:
+//   x[n, h, w, :] = (x + bias[:]) + top[n, sh(h), sw(w), :]      (lateral + bias + interpolate(top, size=(H, W), mode="nearest"))
+// with ATen's nearest source index, src = min(int(floorf(dst * float(in) / out)), in - 1).  Stock PyTorch runs it as a bias add,
+// an upsample that writes a full-size tensor and an add that reads it back (7 tensor passes); this is 2.25.
+template <class L>
+__global__ __launch_bounds__(256) void topdown_merge_kernel(typename L::Raw *__restrict__ x, const float4 *__restrict__ bias,
+                                                           const typename L::Raw *__restrict__ top, int H, int W, int Ht, int Wt, int CV,
+                                                           float scale_h, float scale_w, long long n_vec) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % CV);
+    long long p = i / CV;
+    const int w = (int)(p % W);
+    p /= W;
+    const int h = (int)(p % H);
+    const long long n = p / H;
+    const int sh = min((int)floorf((float)h * scale_h), Ht - 1), sw = min((int)floorf((float)w * scale_w), Wt - 1);
+    float v[L::N], t[L::N];
+    L::unpack(x[i], v);
+    // the source order of the two loads decides the compiler's schedule: each form keeps the one it was measured with
+    auto load_top = [&] { L::unpack(top[((n * Ht + sh) * Wt + sw) * CV + c], t); };
+    if (L::TOP_BEFORE_BIAS) load_top();
+    add_bias<L>(v, bias, c);
+    if (!L::TOP_BEFORE_BIAS) load_top();
+    add<L>(v, t);
+    x[i] = L::pack(v);
+  }
+}
+
+// ResNet stem: bias + ReLU + 3x3 / stride 2 / padding 1 max-pool of the first convolution's output in ONE pass.
+// relu and max commute, so pooled = relu(max over the window of (x + bias)); the backward pass needs, per pooled element, only
+// WHICH window position won (4 bits; 15 = the maximum was not positive, no gradient): the 550 MB activation is neither written
+// back nor re-read, and ATen's int64 index tensor (2 x the pooled output) disappears.  Window scan order and the strict `>`
+// are ATen's (max_pool2d: first maximum in row-major window order).  The 7x7 convolution in front has 3 input channels and stays
+// fp32 in both forms (models/backbone.py): x is fp32, the pooled maximum is stored as L's type, rounded once.  Rounding is
+// monotonic, so the recorded winner is also a maximum of the rounded values.  4 channels per lane.
+template <class L>
+__global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float4 *__restrict__ x, const float4 *__restrict__ bias,
+                                                           typename L::Quad *__restrict__ out, unsigned short *__restrict__ arg, int H,
+                                                           int W, int Ho, int Wo, int C4) {
+  // grid: x over the Wo * C4 float4 of one pooled row, y = pooled row, z = image (no 64-bit divisions on the way to an address)
+  const unsigned col = blockIdx.x * 256u + threadIdx.x;
+  if (col >= (unsigned)(Wo * C4)) return;
+  const int ow = (int)(col / (unsigned)C4), c = (int)(col % (unsigned)C4), oh = blockIdx.y;
+  const size_t n = blockIdx.z;
+  const float4 b = bias[c];
+  const float ninf = -__builtin_inff();
+  float4 m = make_float4(ninf, ninf, ninf, ninf);
+  unsigned ax = 15, ay = 15, az = 15, aw = 15;
+  // all nine loads are issued before the first comparison (clamped addresses, out-of-range positions replaced by -inf): one
+  // memory round trip per thread instead of up to nine dependent ones
+  float4 v[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int h = oh * 2 - 1 + k / 3, w = ow * 2 - 1 + k % 3;
+    const int hc = min(max(h, 0), H - 1), wc = min(max(w, 0), W - 1);
+    v[k] = x[((n * H + hc) * W + wc) * C4 + c];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int h = oh * 2 - 1 + k / 3, w = ow * 2 - 1 + k % 3;
+    const bool in = h >= 0 && h < H && w >= 0 && w < W;
+    const float vx = in ? v[k].x + b.x : ninf, vy = in ? v[k].y + b.y : ninf, vz = in ? v[k].z + b.z : ninf, vw = in ? v[k].w + b.w : ninf;
+    if (vx > m.x) { m.x = vx; ax = k; }
+    if (vy > m.y) { m.y = vy; ay = k; }
+    if (vz > m.z) { m.z = vz; az = k; }
+    if (vw > m.w) { m.w = vw; aw = k; }
+  }
+  if (!(m.x > 0.f)) { m.x = 0.f; ax = 15; }
+  if (!(m.y > 0.f)) { m.y = 0.f; ay = 15; }
+  if (!(m.z > 0.f)) { m.z = 0.f; az = 15; }
+  if (!(m.w > 0.f)) { m.w = 0.f; aw = 15; }
+  const size_t i = ((n * Ho + oh) * Wo) * C4 + col;
+  out[i] = L::pack_quad(m);
+  arg[i] = (unsigned short)(ax | (ay << 4) | (az << 8) | (aw << 12));
+}
+
+// Its backward: the fp32 gradient of the convolution output, dense (every input pixel belongs to at most 2 x 2 windows; it takes
+// the pooled gradient of those whose recorded winner it is, summed in fp32: nothing is rounded).  One pass: pooled gradient + 2
+// bytes per 4 pooled elements in, full-size gradient out -- instead of ATen's max-pool backward plus the ReLU mask pass.
+template <class L>
+__global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const typename L::Quad *__restrict__ g_out, const unsigned short *__restrict__ arg,
+                                                           float4 *__restrict__ g_in, int H, int W, int Ho, int Wo, int C4) {
+  // grid: x over the W * C4 float4 of one input row, y = input row, z = image
+  const unsigned col = blockIdx.x * 256u + threadIdx.x;
+  if (col >= (unsigned)(W * C4)) return;
+  const int w = (int)(col / (unsigned)C4), c = (int)(col % (unsigned)C4), h = blockIdx.y;
+  const size_t n = blockIdx.z;
+  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+  // the (at most) 2 x 2 windows that contain (h, w): oh in {h >> 1, (h + 1) >> 1}, likewise ow; all loads first, then the
+  // selection -- one memory round trip per thread
+  const int ohs[2] = {h >> 1, (h + 1) >> 1}, ows[2] = {w >> 1, (w + 1) >> 1};
+  unsigned a[4];
+  typename L::Quad go[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int oh = min(ohs[q >> 1], Ho - 1), ow = min(ows[q & 1], Wo - 1);
+    const size_t j = ((n * Ho + oh) * Wo + ow) * C4 + c;
+    a[q] = arg[j];
+    go[q] = g_out[j];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int oh = ohs[q >> 1], ow = ows[q & 1];
+    // a window counts once: the second candidate equals the first for even h (w), and must lie inside the pooled image
+    const bool use = oh < Ho && ow < Wo && ((q >> 1) == 0 || ohs[1] != ohs[0]) && ((q & 1) == 0 || ows[1] != ows[0]);
+    const unsigned k = use ? (unsigned)(h - (oh * 2 - 1)) * 3u + (unsigned)(w - (ow * 2 - 1)) : 14u;      // 14: never recorded
+    if ((a[q] & 15u) == k) g.x += L::quad(go[q], 0);
+    if (((a[q] >> 4) & 15u) == k) g.y += L::quad(go[q], 1);
+    if (((a[q] >> 8) & 15u) == k) g.z += L::quad(go[q], 2);
+    if ((a[q] >> 12) == k) g.w += L::quad(go[q], 3);
+  }
+  g_in[((n * H + h) * W) * C4 + col] = g;
+}
+
+// ---- host side: what every entry point of the family does around its kernel -------------------------------------------------------
+typedef std::initializer_list<const void *> Ptrs;
+
+static inline bool misaligned(Ptrs ptrs) {
+  uintptr_t bits = 0;
+  for (const void *p : ptrs) bits |= (uintptr_t)p;
+  return (bits & 15) != 0;
+}
+
+// The checks that follow an entry point's own shape test, in the order callers see them: empty input is DIB_OK, then null
+// pointers, then 16-byte alignment.  True: launch; false: return *code.
+static inline bool args_ok(const char *who, bool empty, Ptrs required, Ptrs aligned, int *code) {
+  *code = empty ? DIB_OK : DIB_EINVAL;
+  if (empty) return false;
+  for (const void *p : required)
+    if (!p) { set_error("%s: null pointer", who); return false; }
+  if (misaligned(aligned)) { set_error("%s: tensors must be 16-byte aligned", who); return false; }
+  return true;
+}
+
+// Launch shape of the streaming kernels: ONE vector per thread (the grid-stride loops only matter past 2^30 workgroups).
+// Measured on the 550 MB tensors of the detector's first pyramid level (scratch/ubench/ub_stream.hip): 185 us (5.9 TB/s) against
+// 220 us (5.0 TB/s) with the grid capped at 32 workgroups per CU (8192 workgroups), 197 against 245 us with the sign mask
+// (docs/measurement_history.md, round 3).
+static inline dim3 grid_1d(long long n_vec) {
+  const long long blocks = (n_vec + 255) / 256;
+  return dim3((unsigned)(blocks > (1ll << 30) ? (1ll << 30) : blocks));
+}
+
+// 256 threads per workgroup; the arguments are converted to the kernel's parameter types (void * to its vector pointers)
+template <typename... P, typename... A>
+static int launch(void (*kernel)(P...), dim3 grid, void *stream, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, (P)args...);
+  DIB_HIP_CHECK(hipGetLastError());
+  return DIB_OK;
+}
+
+// ---- entry points, by lane type (include/dib.h describes them) ------------------------------------------------------------------
+// The vector forms of bias_act; n, CV in vectors.  A mask implies the ReLU.
+template <class L>
+static int bias_act_launch(void *x, const float *bias, const void *res, long long n, int CV, int relu, unsigned char *mask, void *stream) {
+  auto kernel = mask ? (res ? bias_act_kernel<L, true, true, true> : bias_act_kernel<L, false, true, true>)
+                : res ? (relu ? bias_act_kernel<L, true, true, false> : bias_act_kernel<L, true, false, false>)
+                      : (relu ? bias_act_kernel<L, false, true, false> : bias_act_kernel<L, false, false, false>);
+  return launch(kernel, grid_1d(n), stream, x, bias, res, n, CV, mask);
+}
+
+template <class L>
+static int relu_mask_backward(const char *who, const void *grad_in, const unsigned char *mask, void *grad_out, long long n_elems, void *stream) {
+  if (n_elems < 0 || (n_elems % L::N) != 0) { set_error("%s: n_elems must be a non-negative multiple of %d", who, L::N); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, n_elems == 0, {grad_in, mask, grad_out}, {grad_in, grad_out}, &code)) return code;
+  return launch(relu_mask_bwd_kernel<L>, grid_1d(n_elems / L::N), stream, grad_in, mask, grad_out, n_elems / L::N);
+}
+
+template <class L>
+static int add_relu_mask(const char *who, void *a, const void *b, const unsigned char *mask, long long n_elems, void *stream) {
+  if (n_elems < 0 || (n_elems % L::N) != 0) { set_error("%s: n_elems must be a non-negative multiple of %d", who, L::N); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, n_elems == 0, {a, b}, {a, b}, &code)) return code;
+  return launch(mask ? add_mask_kernel<L, true> : add_mask_kernel<L, false>, grid_1d(n_elems / L::N), stream, a, b, mask, n_elems / L::N);
+}
+
+template <class L>
+static int scatter_add(const char *who, void *a, const void *b, int N, int H, int W, int Hs, int Ws, int C, int stride, void *stream) {
+  if (N < 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || (C % L::N) != 0 || stride < 1) { set_error("%s: bad shape (C %% %d == 0)", who, L::N); return DIB_EINVAL; }
+  if ((long long)(Hs - 1) * stride > H - 1 || (long long)(Ws - 1) * stride > W - 1) { set_error("%s: strided grid leaves the target", who); return DIB_ESHAPE; }
+  int code;
+  if (!args_ok(who, N == 0, {a, b}, {a, b}, &code)) return code;
+  const long long n_vec = (long long)N * Hs * Ws * (C / L::N);
+  return launch(scatter_add_kernel<L>, grid_1d(n_vec), stream, a, b, Hs, Ws, C / L::N, H, W, stride, n_vec);
+}
+
+template <class L>
+static int topdown_merge(const char *who, void *x, const float *bias, const void *top, int N, int H, int W, int Ht, int Wt, int C, void *stream) {
+  if (N < 0 || H <= 0 || W <= 0 || Ht <= 0 || Wt <= 0 || C <= 0 || (C % L::N) != 0) { set_error("%s: bad shape (C %% %d == 0)", who, L::N); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, N == 0, {x, bias, top}, {x, bias, top}, &code)) return code;
+  const long long n_vec = (long long)N * H * W * (C / L::N);
+  return launch(topdown_merge_kernel<L>, grid_1d(n_vec), stream, x, bias, top, H, W, Ht, Wt, C / L::N, (float)Ht / (float)H, (float)Wt / (float)W, n_vec);
+}
+
+// Ho = (H - 1) / 2 + 1, Wo likewise; arg: one unsigned short per 4 pooled channels
+template <class L>
+static int stem_pool_forward(const char *who, const float *x, const float *bias, void *out, unsigned short *arg, int N, int H, int W, int C, void *stream) {
+  if (N < 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) != 0) { set_error("%s: bad shape (C %% 4 == 0)", who); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, N == 0, {x, bias, out, arg}, {x, bias, out}, &code)) return code;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  if (Ho > 65535 || N > 65535) { set_error("%s: at most 65535 pooled rows and images per call", who); return DIB_ESHAPE; }
+  return launch(stem_pool_fwd_kernel<L>, dim3((unsigned)((Wo * (C / 4) + 255) / 256), (unsigned)Ho, (unsigned)N), stream, x, bias, out, arg, H, W, Ho, Wo, C / 4);
+}
+
+template <class L>
+static int stem_pool_backward(const char *who, const void *grad_out, const unsigned short *arg, float *grad_in, int N, int H, int W, int C, void *stream) {
+  if (N < 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) != 0) { set_error("%s: bad shape (C %% 4 == 0)", who); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, N == 0, {grad_out, arg, grad_in}, {grad_out, grad_in}, &code)) return code;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  if (H > 65535 || N > 65535) { set_error("%s: at most 65535 rows and images per call", who); return DIB_ESHAPE; }
+  return launch(stem_pool_bwd_kernel<L>, dim3((unsigned)((W * (C / 4) + 255) / 256), (unsigned)H, (unsigned)N), stream, grad_out, arg, grad_in, H, W, Ho, Wo, C / 4);
+}
+
+}  // namespace dib

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import _lib
 from .batchnorm import BatchNorm2d
 
 
@@ -60,25 +61,23 @@ class _BiasAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, residual, relu, state=None):
-        from .. import _lib
         N, C, H, W = x.shape
         stream = _lib.stream_of(x)
         res = residual.data_ptr() if residual is not None else None
         ctx.relu, ctx.has_res, ctx.masked, ctx.state = bool(relu), residual is not None, False, state
-        lp = x.dtype == torch.bfloat16       # bf16 activation, fp32 bias: the 8-per-lane kernels (bias_act checked C % 8 and alignment)
-        if lp:
+        if x.dtype == torch.bfloat16:        # bf16 activation, fp32 bias: the 8-per-lane kernels (bias_act checked C % 8 and alignment)
             LP_CALLS["bias_act"] += 1
         if (relu and RELU_MASK and any(ctx.needs_input_grad[:3]) and C % 4 == 0
                 and not ((x.data_ptr() | bias.data_ptr() | (res or 0)) & 15)):
-            mask = torch.empty(x.numel() // (8 if lp else 4), dtype=torch.uint8, device=x.device)
-            fn = _lib.lib().dib_bias_act_mask_bf16_nhwc if lp else _lib.lib().dib_bias_act_mask_nhwc
+            mask = torch.empty(x.numel() // _lib.LANE[x.dtype], dtype=torch.uint8, device=x.device)
+            fn = _lib.family("bias_act_mask", x.dtype)
             _lib.check(fn(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, mask.data_ptr(), stream))
             ctx.masked = True
             ctx.save_for_backward(mask)
             if state is not None:
                 state["mask"] = mask
         else:
-            fn = _lib.lib().dib_bias_act_bf16_nhwc if lp else _lib.lib().dib_bias_act_nhwc
+            fn = _lib.family("bias_act", x.dtype)
             _lib.check(fn(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, int(relu), stream))
             if relu:
                 ctx.save_for_backward(x)
@@ -93,14 +92,13 @@ class _BiasAct(torch.autograd.Function):
             # of a second consumer's gradient would have bumped its version): the mask was applied while it was accumulated
             pass
         elif ctx.masked:
-            from .. import _lib
             (mask,) = ctx.saved_tensors
             if not grad.is_contiguous(memory_format=torch.channels_last):
                 grad = grad.contiguous(memory_format=torch.channels_last)      # the mask is in NHWC element order
             if grad.data_ptr() & 15:
                 grad = grad.clone(memory_format=torch.channels_last)
             out = torch.empty_like(grad)     # not in place: autograd may hand the same gradient tensor to another node
-            fn = _lib.lib().dib_relu_mask_backward_bf16 if grad.dtype == torch.bfloat16 else _lib.lib().dib_relu_mask_backward
+            fn = _lib.family("relu_mask_backward", grad.dtype)
             _lib.check(fn(grad.data_ptr(), mask.data_ptr(), out.data_ptr(), grad.numel(), _lib.stream_of(grad)))
             grad = out
         elif ctx.relu:
@@ -119,12 +117,12 @@ def _channel_sum(grad):
 
 # how many times a bf16 tensor took each fused path since import (tests count them; nothing reads them on the hot path)
 LP_CALLS = {"bias_act": 0, "block_entry": 0, "down_entry": 0, "topdown_merge": 0, "stem_pool": 0}
-_LP = (torch.float32, torch.bfloat16)
+_LP = tuple(_lib.LANE)      # the activation dtypes the fused paths take
 
 
 def _lp_ok(*tensors):
-    """The bf16 kernels' preconditions beyond the fp32 ones: channel count a multiple of 8, 16-byte aligned."""
-    return all(t.dtype != torch.bfloat16 or (t.shape[1] % 8 == 0 and not (t.data_ptr() & 15)) for t in tensors if t is not None)
+    """The bf16 kernels' preconditions beyond the fp32 ones: channel count a multiple of the lane width (8), 16-byte aligned."""
+    return all(t.dtype != torch.bfloat16 or (t.shape[1] % _lib.LANE[t.dtype] == 0 and not (t.data_ptr() & 15)) for t in tensors if t is not None)
 
 
 def _cast_w(w, dtype):
@@ -344,11 +342,9 @@ class _BlockEntry(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_skip):
-        from .. import _lib
         x, weight = ctx.saved_tensors[:2]
         mask = ctx.saved_tensors[2] if ctx.has_mask else None
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        lp = x.dtype == torch.bfloat16
         if not g_out.is_contiguous(memory_format=torch.channels_last):
             g_out = g_out.contiguous(memory_format=torch.channels_last)
         dx, dw, _ = torch.ops.aten.convolution_backward(g_out, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
@@ -359,10 +355,10 @@ class _BlockEntry(torch.autograd.Function):
             if g_skip is not None:
                 if not g_skip.is_contiguous(memory_format=torch.channels_last) or g_skip.data_ptr() & 15:
                     g_skip = g_skip.clone(memory_format=torch.channels_last)
-                fn = _lib.lib().dib_add_relu_mask_bf16 if lp else _lib.lib().dib_add_relu_mask
+                fn = _lib.family("add_relu_mask", x.dtype)
                 _lib.check(fn(dx.data_ptr(), g_skip.data_ptr(), mask.data_ptr() if mask is not None else None, dx.numel(), _lib.stream_of(dx)))
             elif mask is not None:
-                fn = _lib.lib().dib_relu_mask_backward_bf16 if lp else _lib.lib().dib_relu_mask_backward
+                fn = _lib.family("relu_mask_backward", x.dtype)
                 _lib.check(fn(dx.data_ptr(), mask.data_ptr(), dx.data_ptr(), dx.numel(), _lib.stream_of(dx)))
             if mask is not None:
                 # tell the producing _BiasAct which gradient tensor already carries its ReLU mask; it re-applies the mask (idempotent
@@ -389,7 +385,6 @@ class _DownEntry(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_a, g_d):
-        from .. import _lib
         x, w1, wd = ctx.saved_tensors[:3]
         xs = ctx.saved_tensors[3] if ctx.s != 1 else x
         need_x, need_w1, need_wd = ctx.needs_input_grad[:3]
@@ -400,13 +395,12 @@ class _DownEntry(torch.autograd.Function):
         if need_x:
             dx, dxs = cl(dx), cl(dxs)
             stream = _lib.stream_of(dx)
-            lp = dx.dtype == torch.bfloat16
             if ctx.s == 1:
-                fn = _lib.lib().dib_add_relu_mask_bf16 if lp else _lib.lib().dib_add_relu_mask
+                fn = _lib.family("add_relu_mask", dx.dtype)
                 _lib.check(fn(dx.data_ptr(), dxs.data_ptr(), None, dx.numel(), stream))
             else:
                 N, C, H, W = dx.shape
-                fn = _lib.lib().dib_scatter_add_bf16_nhwc if lp else _lib.lib().dib_scatter_add_nhwc
+                fn = _lib.family("scatter_add", dx.dtype)
                 _lib.check(fn(dx.data_ptr(), dxs.data_ptr(), N, H, W, dxs.shape[2], dxs.shape[3], C, ctx.s, stream))
         return (dx if need_x else None), (dw1 if need_w1 else None), (dwd if need_wd else None), None, None
 
@@ -421,7 +415,6 @@ FOLD_ALL = True
 class _FoldAll(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pairs, *weights):
-        from .. import _lib
         n = len(weights)
         dev = weights[0].device
         cos = [int(w.shape[0]) for w in weights]
@@ -445,7 +438,6 @@ class _FoldAll(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        from .. import _lib
         (flat,) = ctx.saved_tensors
         cos, inner = ctx.meta
         n = len(cos)
@@ -718,7 +710,6 @@ PLANAR_FUSED = True      # inference: the layout changes around planar 3x3 convo
 def bias_act_transpose(x, bias, relu, to_planar):
     """act(x + bias) of a channels-last tensor written planar (to_planar) or of a planar tensor written channels-last: one pass
     (csrc/dib_eltwise.hip) for what bias_act + .contiguous(...) do in two."""
-    from .. import _lib
     N, C, H, W = x.shape
     out = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device,
                       memory_format=torch.contiguous_format if to_planar else torch.channels_last)
@@ -784,12 +775,11 @@ class _StemPool(torch.autograd.Function):
     def forward(ctx, x, bias, out_dtype=torch.float32):
         # x is the fp32 convolution output; out_dtype bf16: the pooled tensor is stored as bf16 (one rounding) and the backward
         # pass reads a bf16 gradient -- the dense gradient it writes is the fp32 convolution's, fp32 either way
-        from .. import _lib
         N, C, H, W = x.shape
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         out = torch.empty((N, C, Ho, Wo), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
         arg = torch.empty((N * Ho * Wo * (C // 4),), dtype=torch.int16, device=x.device)
-        fn = _lib.lib().dib_stem_pool_forward_bf16 if out_dtype == torch.bfloat16 else _lib.lib().dib_stem_pool_forward
+        fn = _lib.family("stem_pool_forward", out_dtype)
         _lib.check(fn(x.data_ptr(), bias.data_ptr(), out.data_ptr(), arg.data_ptr(), N, H, W, C, _lib.stream_of(x)))
         ctx.shape = (N, C, H, W)
         ctx.save_for_backward(arg)
@@ -797,13 +787,12 @@ class _StemPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib
         (arg,) = ctx.saved_tensors
         N, C, H, W = ctx.shape
         if not g.is_contiguous(memory_format=torch.channels_last) or (g.data_ptr() & 15):
             g = g.clone(memory_format=torch.channels_last)
         gx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
-        fn = _lib.lib().dib_stem_pool_backward_bf16 if g.dtype == torch.bfloat16 else _lib.lib().dib_stem_pool_backward
+        fn = _lib.family("stem_pool_backward", g.dtype)
         _lib.check(fn(g.data_ptr(), arg.data_ptr(), gx.data_ptr(), N, H, W, C, _lib.stream_of(g)))
         return gx, (gx.sum(dim=(0, 2, 3)) if ctx.needs_input_grad[1] else None), None
 
@@ -876,11 +865,10 @@ class _TopDownMerge(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, top):
-        from .. import _lib
         N, C, H, W = x.shape
         ctx.top_shape = tuple(top.shape)
         ctx.mark_dirty(x)
-        fn = _lib.lib().dib_fpn_topdown_merge_bf16_nhwc if x.dtype == torch.bfloat16 else _lib.lib().dib_fpn_topdown_merge_nhwc
+        fn = _lib.family("topdown_merge", x.dtype)
         _lib.check(fn(x.data_ptr(), bias.data_ptr(), top.data_ptr(), N, H, W, top.shape[2], top.shape[3], C, _lib.stream_of(x)))
         return x
 

@@ -1,5 +1,5 @@
 // Micro-benchmark (not product code): in-place bias + ReLU epilogue over a 550 MB channels-last tensor (8 x 256 x 200 x 336 fp32),
-// the shape of dib_eltwise.hip's bias_act_vec4_kernel: grid-stride with a capped grid vs one float4 per thread, 64-bit vs 32-bit
+// the shape of dib_eltwise_vec.h's bias_act_kernel: grid-stride with a capped grid vs one float4 per thread, 64-bit vs 32-bit
 // index arithmetic, with and without the sign mask.
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -257,15 +257,79 @@ def test_abi_lists_the_bf16_epilogues():
     assert l.dib_bias_act_bf16_nhwc(None, None, None, 64, 16, 1, None) == _lib.DIB_EINVAL and b"null pointer" in l.dib_last_error()
     assert l.dib_add_relu_mask_bf16(None, None, None, 12, None) == _lib.DIB_EINVAL and b"multiple of 8" in l.dib_last_error()
     assert l.dib_scatter_add_bf16_nhwc(16, 16, 1, 4, 4, 3, 3, 8, 2, None) == _lib.DIB_ESHAPE
+    # every argument error of both forms of the family: the code, the entry point's own name in front, and the order in which
+    # the conditions are tested.  Integers stand in for device pointers (16 = aligned; 17, 24, 40 = not): each row is refused
+    # (or found empty) before anything is launched.  dib_bias_act_nhwc has no misalignment row: its answer is the scalar kernel.
+    EINVAL, ESHAPE, OK = _lib.DIB_EINVAL, _lib.DIB_ESHAPE, 0
+    rows = []
+    for sfx, n, bad in (("", 4, 6), ("_bf16", 8, 12)):
+        mult = b"n_elems must be a non-negative multiple of %d" % n
+        shape = b"_nhwc: bad shape (C %% %d == 0)" % n
+        rows += [
+            ("dib_relu_mask_backward" + sfx, (None, None, None, bad, None), EINVAL, mult),
+            ("dib_relu_mask_backward" + sfx, (16, 16, 16, -n, None), EINVAL, mult),
+            ("dib_relu_mask_backward" + sfx, (17, None, None, 0, None), OK, None),
+            ("dib_relu_mask_backward" + sfx, (16, None, 16, 2 * n, None), EINVAL, b"dib_relu_mask_backward%s: null pointer" % sfx.encode()),
+            ("dib_relu_mask_backward" + sfx, (16, 3, 17, 2 * n, None), EINVAL, b"dib_relu_mask_backward%s: tensors must be 16-byte aligned" % sfx.encode()),
+            ("dib_add_relu_mask" + sfx, (None, None, None, bad, None), EINVAL, b"dib_add_relu_mask%s: " % sfx.encode() + mult),
+            ("dib_add_relu_mask" + sfx, (None, None, None, 0, None), OK, None),
+            ("dib_add_relu_mask" + sfx, (None, 16, None, 2 * n, None), EINVAL, b"dib_add_relu_mask%s: null pointer" % sfx.encode()),
+            ("dib_add_relu_mask" + sfx, (16, 24, None, 2 * n, None), EINVAL, b"dib_add_relu_mask%s: tensors must be 16-byte aligned" % sfx.encode()),
+            # a, b, N, H, W, Hs, Ws, C, stride: bad shape, then the strided grid (even for N == 0), then N == 0, then the pointers
+            ("dib_scatter_add%s_nhwc" % sfx, (16, 16, 1, 4, 4, 2, 2, bad, 2, None), EINVAL, b"dib_scatter_add" + sfx.encode() + shape),
+            ("dib_scatter_add%s_nhwc" % sfx, (16, 16, 1, 4, 4, 2, 2, 2 * n, 0, None), EINVAL, b"dib_scatter_add" + sfx.encode() + shape),
+            ("dib_scatter_add%s_nhwc" % sfx, (None, None, 0, 4, 4, 3, 3, 2 * n, 2, None), ESHAPE, b"dib_scatter_add%s_nhwc: strided grid leaves the target" % sfx.encode()),
+            ("dib_scatter_add%s_nhwc" % sfx, (None, None, 0, 4, 4, 2, 2, 2 * n, 2, None), OK, None),
+            ("dib_scatter_add%s_nhwc" % sfx, (None, 16, 1, 4, 4, 2, 2, 2 * n, 2, None), EINVAL, b"dib_scatter_add%s_nhwc: null pointer" % sfx.encode()),
+            ("dib_scatter_add%s_nhwc" % sfx, (16, 24, 1, 4, 4, 2, 2, 2 * n, 2, None), EINVAL, b"dib_scatter_add%s_nhwc: tensors must be 16-byte aligned" % sfx.encode()),
+            # x, bias, top, N, H, W, Ht, Wt, C
+            ("dib_fpn_topdown_merge%s_nhwc" % sfx, (16, 16, 16, 1, 4, 4, 2, 2, bad, None), EINVAL, b"dib_fpn_topdown_merge" + sfx.encode() + shape),
+            ("dib_fpn_topdown_merge%s_nhwc" % sfx, (None, None, None, 0, 4, 4, 2, 2, 2 * n, None), OK, None),
+            ("dib_fpn_topdown_merge%s_nhwc" % sfx, (16, 16, None, 1, 4, 4, 2, 2, 2 * n, None), EINVAL, b"dib_fpn_topdown_merge%s_nhwc: null pointer" % sfx.encode()),
+            ("dib_fpn_topdown_merge%s_nhwc" % sfx, (16, 16, 40, 1, 4, 4, 2, 2, 2 * n, None), EINVAL, b"dib_fpn_topdown_merge%s_nhwc: tensors must be 16-byte aligned" % sfx.encode()),
+            # the stem pool takes 4 channels per lane in both forms: x, bias, out, arg, N, H, W, C / grad_out, arg, grad_in, N, H, W, C
+            ("dib_stem_pool_forward" + sfx, (16, 16, 16, 16, 1, 8, 8, 6, None), EINVAL, b"dib_stem_pool_forward%s: bad shape (C %% 4 == 0)" % sfx.encode()),
+            ("dib_stem_pool_forward" + sfx, (None, None, None, None, 0, 8, 8, 4, None), OK, None),
+            ("dib_stem_pool_forward" + sfx, (16, 16, 16, None, 1, 8, 8, 4, None), EINVAL, b"dib_stem_pool_forward%s: null pointer" % sfx.encode()),
+            ("dib_stem_pool_forward" + sfx, (16, 16, 24, 16, 1, 131071, 8, 4, None), EINVAL, b"dib_stem_pool_forward%s: tensors must be 16-byte aligned" % sfx.encode()),
+            ("dib_stem_pool_forward" + sfx, (16, 16, 16, 16, 1, 131071, 8, 4, None), ESHAPE, b"dib_stem_pool_forward%s: at most 65535 pooled rows and images per call" % sfx.encode()),
+            ("dib_stem_pool_forward" + sfx, (16, 16, 16, 16, 65536, 8, 8, 4, None), ESHAPE, b"dib_stem_pool_forward%s: at most 65535 pooled rows" % sfx.encode()),
+            ("dib_stem_pool_backward" + sfx, (16, 16, 16, 1, 8, 8, 6, None), EINVAL, b"dib_stem_pool_backward%s: bad shape (C %% 4 == 0)" % sfx.encode()),
+            ("dib_stem_pool_backward" + sfx, (None, None, None, 0, 8, 8, 4, None), OK, None),
+            ("dib_stem_pool_backward" + sfx, (16, None, 16, 1, 8, 8, 4, None), EINVAL, b"dib_stem_pool_backward%s: null pointer" % sfx.encode()),
+            ("dib_stem_pool_backward" + sfx, (24, 16, 16, 1, 65536, 8, 4, None), EINVAL, b"dib_stem_pool_backward%s: tensors must be 16-byte aligned" % sfx.encode()),
+            ("dib_stem_pool_backward" + sfx, (16, 16, 16, 1, 65536, 8, 4, None), ESHAPE, b"dib_stem_pool_backward%s: at most 65535 rows and images per call" % sfx.encode()),
+            ("dib_stem_pool_backward" + sfx, (16, 16, 16, 65536, 8, 8, 4, None), ESHAPE, b"dib_stem_pool_backward%s: at most 65535 rows" % sfx.encode()),
+        ]
+    rows += [
+        # x, bias, residual, n_elems, C, relu | mask.  The fp32 pair reports the shared checks under dib_bias_act_nhwc's name
+        ("dib_bias_act_nhwc", (16, 16, None, 50, 12, 1, None), EINVAL, b"dib_bias_act_nhwc: n_elems must be a multiple of C"),
+        ("dib_bias_act_nhwc", (16, 16, None, 48, 0, 1, None), EINVAL, b"dib_bias_act_nhwc: n_elems must be a multiple of C"),
+        ("dib_bias_act_nhwc", (None, None, None, 0, 12, 1, None), OK, None),
+        ("dib_bias_act_nhwc", (16, None, None, 48, 12, 1, None), EINVAL, b"dib_bias_act_nhwc: null pointer"),
+        ("dib_bias_act_mask_nhwc", (16, 16, None, 64, 16, None, None), EINVAL, b"dib_bias_act_mask_nhwc: null mask pointer"),
+        ("dib_bias_act_mask_nhwc", (16, 16, None, 60, 6, 16, None), EINVAL, b"dib_bias_act_mask_nhwc: needs C % 4 == 0 and 16-byte aligned tensors"),
+        ("dib_bias_act_mask_nhwc", (16, 16, 17, 64, 16, 16, None), EINVAL, b"dib_bias_act_mask_nhwc: needs C % 4 == 0 and 16-byte aligned tensors"),
+        ("dib_bias_act_mask_nhwc", (16, 16, None, 50, 16, 16, None), EINVAL, b"dib_bias_act_nhwc: n_elems must be a multiple of C"),
+        ("dib_bias_act_mask_nhwc", (None, 16, None, 0, 16, 16, None), OK, None),
+        ("dib_bias_act_mask_nhwc", (None, 16, None, 64, 16, 16, None), EINVAL, b"dib_bias_act_nhwc: null pointer"),
+        ("dib_bias_act_bf16_nhwc", (16, 16, None, 50, 16, 1, None), EINVAL, b"dib_bias_act_bf16_nhwc: needs C % 8 == 0 and n_elems a multiple of C"),
+        ("dib_bias_act_bf16_nhwc", (17, None, None, 0, 16, 1, None), OK, None),
+        ("dib_bias_act_bf16_nhwc", (16, 16, 24, 64, 16, 1, None), EINVAL, b"dib_bias_act_bf16_nhwc: tensors must be 16-byte aligned"),
+        ("dib_bias_act_mask_bf16_nhwc", (16, 16, None, 48, 12, None, None), EINVAL, b"dib_bias_act_mask_bf16_nhwc: null mask pointer"),
+        ("dib_bias_act_mask_bf16_nhwc", (16, 16, None, 48, 12, 16, None), EINVAL, b"dib_bias_act_mask_bf16_nhwc: needs C % 8 == 0"),
+        ("dib_bias_act_mask_bf16_nhwc", (16, None, None, 64, 16, 16, None), EINVAL, b"dib_bias_act_mask_bf16_nhwc: null pointer"),
+        ("dib_bias_act_mask_bf16_nhwc", (17, 16, None, 64, 16, 16, None), EINVAL, b"dib_bias_act_mask_bf16_nhwc: tensors must be 16-byte aligned"),
+    ]
+    for name, args, code, text in rows:
+        assert getattr(l, name)(*args) == code, (name, args, l.dib_last_error())
+        assert text is None or text in l.dib_last_error(), (name, args, l.dib_last_error())
 
 
-def test_bf16_kernels_use_no_scratch():
-    """The check of tests/test_mode_one_norm.py::test_mode_one_kernels_use_no_scratch on the bf16 epilogues, and that the one
-    rounding per element is the packed hardware conversion."""
-    if not os.path.isfile(HIPCC):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "detectinblur_amd", "csrc", "dib_eltwise_bf16.hip")
-    asm = os.path.join(os.environ.get("TMPDIR", "/tmp"), "dib_eltwise_bf16_%d.s" % os.getpid())
+def _device_asm(name):
+    """(kernel -> {ScratchSize, Occupancy}, assembly text) of one csrc file compiled for gfx950 with the library's flags."""
+    src = os.path.join(ROOT, "detectinblur_amd", "csrc", name)
+    asm = os.path.join(os.environ.get("TMPDIR", "/tmp"), "%s_%d.s" % (name, os.getpid()))
     try:
         p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S", src,
                             "-o", asm, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
@@ -283,13 +347,30 @@ def test_bf16_kernels_use_no_scratch():
         m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    for frag in ("bias_act_bf16_kernel", "relu_mask_bwd_bf16_kernel", "add_mask_bf16_kernel", "scatter_add_bf16_kernel",
-                 "topdown_merge_bf16_kernel", "stem_pool_fwd_bf16_kernel", "stem_pool_bwd_bf16_kernel"):
-        names = [n for n in out if frag in n]
-        assert names, frag
-        for n in names:
-            assert out[n]["ScratchSize"] == 0, (n, out[n])
-            assert out[n]["Occupancy"] >= 4, (n, out[n])
-    assert "v_cvt_pk_bf16_f32" in text
-    assert "global_load_dwordx4" in text and "global_store_dwordx4" in text        # 16-byte accesses
-    assert "global_atomic" not in text and "flat_atomic" not in text
+    return out, text
+
+
+def test_bf16_kernels_use_no_scratch():
+    """The check of tests/test_mode_one_norm.py::test_mode_one_kernels_use_no_scratch on the epilogue family (the templates of
+    csrc/dib_eltwise_vec.h as instantiated for bf16, and for fp32), and that the one rounding per bf16 element is the packed
+    hardware conversion."""
+    if not os.path.isfile(HIPCC):
+        pytest.skip("hipcc not available")
+    # kernel stem -> instantiations per lane type (bias_act: residual x ReLU, and the two masked forms; add_mask: with and without)
+    family = {"bias_act_kernel": 6, "relu_mask_bwd_kernel": 1, "add_mask_kernel": 2, "scatter_add_kernel": 1,
+              "topdown_merge_kernel": 1, "stem_pool_fwd_kernel": 1, "stem_pool_bwd_kernel": 1}
+    for name, lane in (("dib_eltwise_bf16.hip", "Bf16Lane"), ("dib_eltwise.hip", "F32Lane")):
+        out, text = _device_asm(name)
+        other = "F32Lane" if lane == "Bf16Lane" else "Bf16Lane"
+        assert not [n for n in out if other in n], name               # the text checks below look at one type's code only
+        for frag, count in family.items():
+            names = [n for n in out if frag in n and lane in n]
+            assert len(names) == count, (frag, names)
+            for n in names:
+                assert out[n]["ScratchSize"] == 0, (n, out[n])
+                assert out[n]["Occupancy"] >= 4, (n, out[n])
+        if lane == "Bf16Lane":
+            assert len(out) == sum(family.values()), sorted(out)      # nothing but the family in this file
+            assert "v_cvt_pk_bf16_f32" in text
+            assert "global_load_dwordx4" in text and "global_store_dwordx4" in text        # 16-byte accesses
+            assert "global_atomic" not in text and "flat_atomic" not in text
