@@ -361,7 +361,8 @@ def _nms_torch(boxes, scores, thr):
 
 
 def nms(boxes, scores, iou_threshold):
-    """Indices of the boxes that survive greedy NMS, by descending score."""
+    """Indices of the boxes that survive greedy NMS, by descending score.  On the GPU only the 16384 boxes with the
+    highest scores take part (the kernels' limit): any further box is dropped, neither kept nor suppressing."""
     if boxes.numel() == 0:
         return torch.empty((0,), dtype=torch.int64, device=boxes.device)
     if not boxes.is_cuda:

@@ -817,3 +817,255 @@ def jpeg_roundtrip64(img, quality, pad=True):
     hi = np.abs(out) + flip + err
     half_ulp = np.spacing(hi.astype(np.float16)).astype(np.float64) / 2       # the final cast to fp16
     return out, flip + err + half_ulp, exact
+
+
+# --------------------------------------------------------------------------------------
+# A17 RoIAlign and greedy NMS: float64 / exact-integer references for csrc/dib_roi.hip
+#     (torchvision.ops.roi_align / nms, which reference models/faster_rcnn.py:204-208 and its RPN / RoIHeads call)
+# --------------------------------------------------------------------------------------
+# Written from the published Detectron / torchvision definition, not from the kernels.  Per RoI (batch index, x1, y1,
+# x2, y2) on an H x W map: corners times spatial_scale (minus 0.5 when aligned); width / height clamped to >= 1 unless
+# aligned; P x P bins; per bin a gh x gw grid of samples at bin start + (i + 0.5) * bin / g, g = sampling_ratio or,
+# when that is <= 0, ceil(size / P) per axis; a sample with y < -1, y > H, x < -1 or x > W counts 0, every other one is
+# the bilinear interpolation at (max(y, 0), max(x, 0)) with the last row / column repeated beyond H - 1 / W - 1; the bin
+# is the sum over max(gh * gw, 1).  All arithmetic in float64 from the float32 inputs.
+
+def _roi_axis(lo, bin_, P, g, L, guard, force):
+    """Sample coordinates of one axis for K RoIs with a common grid g: [K, P * g] -> inside, near, i0, i1, w0, w1."""
+    frac = (np.arange(P)[:, None] + (np.arange(g)[None, :] + 0.5) / g).reshape(-1)
+    t = lo[:, None] + frac[None, :] * bin_[:, None]
+    near = (np.abs(t + 1.0) < guard) | (np.abs(t - L) < guard)
+    ok = (t >= -1.0) & (t <= L)
+    if force == "in":
+        ok = ok | near
+    elif force == "out":
+        ok = ok & ~near
+    tc = np.maximum(t, 0.0)
+    i0 = np.floor(tc).astype(np.int64)
+    top = i0 >= L - 1
+    i0 = np.where(top, L - 1, i0)
+    i1 = np.where(top, L - 1, i0 + 1)
+    w1 = np.where(top, 0.0, tc - i0)
+    return t, ok, near, i0, i1, 1.0 - w1, w1
+
+
+def _dyadic_q(a, qmax=40):
+    """Smallest q with every element of a a multiple of 2^-q (qmax + 1 if there is none up to qmax)."""
+    a = np.abs(np.asarray(a, dtype=np.float64).ravel())
+    a = a[a != 0]
+    for q in range(qmax + 1):
+        s = np.ldexp(a, q)
+        if np.array_equal(s, np.rint(s)):
+            return q
+    return qmax + 1
+
+
+def _scatter_add(dst, idx, vals):
+    """dst[idx[i]] += vals[i] (rows), duplicates included: sort + segment sums instead of np.add.at."""
+    if idx.size == 0:
+        return
+    order = np.argsort(idx, kind="stable")
+    idx, vals = idx[order], vals[order]
+    starts = np.flatnonzero(np.r_[True, idx[1:] != idx[:-1]])
+    dst[idx[starts]] += np.add.reduceat(vals, starts, axis=0)
+
+
+def _roi_geometry(rois, scale, P, sr, aligned, guard):
+    r = np.asarray(rois, dtype=np.float32).astype(np.float64)
+    s = float(np.float32(scale))
+    off = 0.5 if aligned else 0.0
+    x1, y1, x2, y2 = (r[:, i] * s - off for i in (1, 2, 3, 4))
+    rw, rh = x2 - x1, y2 - y1
+    raw = np.stack([rh, rw], 1)
+    if not aligned:
+        rw, rh = np.maximum(rw, 1.0), np.maximum(rh, 1.0)
+    bh, bw = rh / P, rw / P
+    K = r.shape[0]
+    if sr > 0:
+        grid = np.full((K, 2), sr, dtype=np.int64)
+        alt = grid.copy()
+    else:
+        v = np.stack([bh, bw], 1)
+        grid = np.ceil(v).astype(np.int64)
+        n = np.rint(v)
+        amb = np.abs(v - n) < guard
+        alt = np.where(amb, np.where(grid == n, n + 1, n), grid).astype(np.int64)
+    return dict(b=r[:, 0].astype(np.int64), x1=x1, y1=y1, bw=bw, bh=bh, grid=grid, grid_alt=alt, raw=raw)
+
+
+def _roi_level(F, G, S, geo, sel, P, gh, gw, guard, force, gout, res, exact, lv):
+    """RoIs `sel` (indices into the call's RoI list; all of level lv, all with the grid gh x gw); geo holds their geometry.
+    F [N, H, W, C] float64 features (forward) or None; G, S [N*H*W, C] gradient / error-scale accumulators (backward)."""
+    N, H, W, C = res["shape"]
+    K = sel.size
+    cnt = float(max(gh * gw, 1))
+    ty, oky, ny, Y0, Y1, hy, ly = _roi_axis(geo["y1"], geo["bh"], P, max(gh, 0), H, guard, force)
+    tx, okx, nx, X0, X1, hx, lx = _roi_axis(geo["x1"], geo["bw"], P, max(gw, 0), W, guard, force)
+    for j, k in enumerate(sel):
+        res["y"][k], res["x"][k] = ty[j], tx[j]
+    if gh <= 0 or gw <= 0:
+        return
+    R, Q = P * gh, P * gw
+    ok = oky[:, :, None] & okx[:, None, :]
+    res["near"][sel] |= (ny[:, :, None] | nx[:, None, :]).reshape(K, P, gh, P, gw).any(axis=(2, 4))
+    b = geo["b"][:, None, None]
+    corners = [(Y0, hy, X0, hx), (Y0, hy, X1, lx), (Y1, ly, X0, hx), (Y1, ly, X1, lx)]
+    if F is not None:
+        acc = np.zeros((K, R, Q, C))
+        mag = np.zeros((K, R, Q, C))
+        tot = np.zeros((K, R, Q, C))
+        for Ya, wy, Xb, wx in corners:
+            v = F[b, Ya[:, :, None], Xb[:, None, :]]
+            w = (wy[:, :, None] * wx[:, None, :] * ok)[..., None]
+            acc += w * v
+            np.maximum(mag, np.abs(v) * ok[..., None], out=mag)
+            if exact is not None:
+                exact["q_fwd"] = max(exact["q_fwd"], _dyadic_q(w) + exact["q_feat"])      # >= that of the products
+                tot += np.abs(w * v)
+        bins = lambda a, f: f(a.reshape(K, P, gh, P, gw, C), axis=(2, 4)).transpose(0, 3, 1, 2)    # noqa: E731
+        res["out"][sel] = bins(acc, np.sum) / cnt
+        res["scale"][sel] = bins(mag, np.max)
+        if exact is not None:
+            exact["sum_fwd"] = max(exact["sum_fwd"], float(bins(tot, np.sum).max()))
+    if G is not None:
+        go = np.asarray(gout)[sel].astype(np.float64).transpose(0, 2, 3, 1) / cnt                  # [K, P, P, C]
+        go = np.broadcast_to(go[:, :, None, :, None, :], (K, P, gh, P, gw, C)).reshape(K, R, Q, C)
+        q_go = _dyadic_q(go[:, ::gh, ::gw]) if exact is not None else 0
+        for n, (Ya, wy, Xb, wx) in enumerate(corners):
+            idx = ((b * H + Ya[:, :, None]) * W + Xb[:, None, :]).reshape(-1)
+            w = (wy[:, :, None] * wx[:, None, :] * ok)[..., None]
+            _scatter_add(G, idx, (w * go).reshape(-1, C))
+            # the scale counts a sample once per cell it touches: the repeated last row / column is one cell
+            touch = ok.copy()
+            if n >= 2:
+                touch &= (Y1 != Y0)[:, :, None]
+            if n % 2:
+                touch &= (X1 != X0)[:, None, :]
+            _scatter_add(S, idx, (np.abs(go) * touch[..., None]).reshape(-1, C))
+            if exact is not None:
+                exact["q_bwd"] = max(exact["q_bwd"], _dyadic_q(w) + q_go)
+                _scatter_add(exact["cells"][lv], idx, np.abs(w * go).reshape(-1, C))
+
+
+def _roi_run(feats, shapes, gout, rois, scale, pooled, sampling_ratio, aligned, level, guard, force, grid, exact):
+    single = level is None
+    scales = [scale] if np.isscalar(scale) else list(scale)
+    rois = np.asarray(rois, dtype=np.float32).reshape(-1, 5)
+    K, P = rois.shape[0], int(pooled)
+    lvl = np.zeros(K, dtype=np.int64) if single else np.clip(np.asarray(level, dtype=np.int64), 0, len(shapes) - 1)
+    C = shapes[0][1]
+    res = dict(out=np.zeros((K, C, P, P)), scale=np.zeros((K, C, P, P)), near=np.zeros((K, P, P), dtype=bool),
+               y=[None] * K, x=[None] * K, grid=np.zeros((K, 2), dtype=np.int64), grid_alt=np.zeros((K, 2), dtype=np.int64),
+               raw=np.zeros((K, 2)), grad=[], gscale=[])
+    ex = None
+    if exact:
+        ex = dict(q_fwd=0, q_feat=0, sum_fwd=0.0, q_bwd=0, q_geom=0, max_coord=0.0, cells=[np.zeros((s[0] * s[2] * s[3], C)) for s in shapes])
+        res["exact"] = ex
+    for lv, shape in enumerate(shapes):
+        N, _, H, W = shape
+        res["shape"] = (N, H, W, C)
+        F = None if feats is None else np.ascontiguousarray(np.asarray(feats[lv], dtype=np.float32).astype(np.float64).transpose(0, 2, 3, 1))
+        if ex is not None and F is not None:
+            ex["q_feat"] = _dyadic_q(F)
+        G = S = None
+        if gout is not None:
+            G, S = np.zeros((N * H * W, C)), np.zeros((N * H * W, C))
+        here = np.flatnonzero(lvl == lv)
+        if here.size:
+            geo = _roi_geometry(rois[here], scales[lv], P, sampling_ratio, aligned, guard)
+            res["grid"][here], res["grid_alt"][here], res["raw"][here] = geo["grid"], geo["grid_alt"], geo["raw"]
+            res["near"][here[(geo["grid"] != geo["grid_alt"]).any(axis=1)]] = True
+            if ex is not None:
+                g = np.concatenate([geo[k] for k in ("x1", "y1", "bw", "bh")])
+                ex["q_geom"] = max(ex["q_geom"], _dyadic_q(g))
+                ex["max_coord"] = max(ex["max_coord"], float(np.abs(g).max()))
+            use = geo["grid"] if grid is None else np.asarray(grid, dtype=np.int64)[here]
+            for gh, gw in sorted(set(map(tuple, use.tolist()))):
+                loc = np.flatnonzero((use[:, 0] == gh) & (use[:, 1] == gw))
+                step = max(1, int(4e6 // (P * P * max(gh, 1) * max(gw, 1) * C)))
+                for s0 in range(0, loc.size, step):
+                    part = loc[s0:s0 + step]
+                    _roi_level(F, G, S, {k: v[part] for k, v in geo.items()}, here[part], P, gh, gw, guard, force, gout, res, ex, lv)
+        if gout is not None:
+            res["grad"].append(G.reshape(N, H, W, C).transpose(0, 3, 1, 2))
+            res["gscale"].append(S.reshape(N, H, W, C).transpose(0, 3, 1, 2))
+    if ex is not None:
+        ex["sum_bwd"] = max(float(c.max()) if c.size else 0.0 for c in ex["cells"])
+        del ex["cells"]
+    del res["shape"]
+    if gout is None:
+        del res["grad"], res["gscale"]
+    elif single:
+        res["grad"], res["gscale"] = res["grad"][0], res["gscale"][0]
+    return res
+
+
+def roi_align64(feat, rois, scale, pooled, sampling_ratio, aligned, level=None, guard=0.0, force="ref", grid=None,
+                exact=False):
+    """RoIAlign as defined above.  feat [N, C, H, W] float32 with a scalar scale, or a list of levels with a list of
+    scales and `level` [K] (the level each RoI pools from).  Returns a dict:
+      out    [K, C, P, P] float64;
+      near   [K, P, P] bool -- the bin has a sample within `guard` of y = -1, y = H, x = -1 or x = W (the only points where
+             the definition is discontinuous in the coordinates) or, with adaptive sampling, the RoI's grid != grid_alt;
+      scale  [K, C, P, P] -- the largest |feature value| the element's samples touch (its error scale);
+      y, x   per RoI, the float64 sample coordinates of the two axes (P * gh and P * gw of them);
+      grid   [K, 2] (gh, gw);  grid_alt [K, 2]: where size / P lies within `guard` of an integer, the other grid size a
+             float32 evaluation may arrive at (equal to grid elsewhere);  raw [K, 2]: (height, width) before the clamp.
+    force = "in" / "out" evaluates the samples within the guard as inside / outside; grid = [K, 2] overrides the grid.
+    exact=True adds `exact`: q_fwd with every term weight * feature a multiple of 2^-q_fwd (the smallest such q of the
+    weights plus that of the features), the largest
+    sum of |terms| of one output (sum_fwd), and q_geom / max_coord for the RoI geometry."""
+    feats = [feat] if level is None else list(feat)
+    shapes = [tuple(np.asarray(f).shape) for f in feats]
+    return _roi_run(feats, shapes, None, rois, scale, pooled, sampling_ratio, aligned, level, guard, force, grid, exact)
+
+
+def roi_align_backward64(gout, shape, rois, scale, pooled, sampling_ratio, aligned, level=None, guard=0.0, force="ref",
+                         grid=None, exact=False):
+    """The transpose of roi_align64: gout [K, C, P, P] -> grad [N, C, H, W] float64 (a list with `level`); `shape` is the
+    feature shape (a list of shapes with `level`).  Also `gscale`, per feature cell the sum of |gout| / count over the
+    samples that touch it (unweighted: a weight near 0 still carries the absolute coordinate error), and with
+    exact=True q_bwd / sum_bwd: the terms weight * gout / count and their largest sum of magnitudes per feature cell."""
+    shapes = [tuple(shape)] if level is None else [tuple(s) for s in shape]
+    return _roi_run(None, shapes, gout, rois, scale, pooled, sampling_ratio, aligned, level, guard, force, grid, exact)
+
+
+def nms_greedy(boxes, valid, thr):
+    """Greedy NMS over integer-coordinate boxes [n, 4] (x1, y1, x2, y2) given in score order; valid [n] bool or None.
+    Returns the kept positions.  Box i, once kept, removes every later j with IoU(i, j) > thr; an invalid box is never
+    kept and never removes.  The decision is made on exact integers:
+      inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0), union = area_i + area_j - inter, area = (x2 - x1) *
+      (y2 - y1) unclamped as in torchvision's box_iou (a box with two negative sides has a positive area);
+      inter == 0 never removes: 0 / union is 0, -0 or (zero-area boxes, 0 / 0) NaN, and none of them is > thr >= 0;
+      inter > 0 means both boxes have positive sides, so union > 0: thr = 0.5 decides by 2 * inter > union, any other
+      threshold by the one correctly rounded division float32(inter) / float32(union) > float32(thr)."""
+    b = np.asarray(boxes)
+    assert np.array_equal(b, np.rint(b)) and thr >= 0
+    b = b.astype(np.int64)
+    n = b.shape[0]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    assert n == 0 or (np.abs(b).max() < 2 ** 24 and np.abs(area).max() < 2 ** 23), "every float32 step must be exact"
+    removed = np.zeros(n, dtype=bool) if valid is None else ~np.asarray(valid, dtype=bool)
+    keep = []
+    t32 = np.float32(thr)
+    for i in range(n):
+        if removed[i]:
+            continue
+        keep.append(i)
+        r = b[i + 1:]
+        iw = np.minimum(b[i, 2], r[:, 2]) - np.maximum(b[i, 0], r[:, 0])
+        cand = np.flatnonzero(iw > 0)
+        if cand.size == 0:
+            continue
+        r = r[cand]
+        ih = np.minimum(b[i, 3], r[:, 3]) - np.maximum(b[i, 1], r[:, 1])
+        inter = iw[cand] * np.maximum(ih, 0)
+        union = area[i] + area[i + 1:][cand] - inter
+        pos = inter > 0
+        assert (union[pos] > 0).all() and (union[pos] < 2 ** 24).all()
+        if thr == 0.5:
+            sup = pos & (2 * inter > union)
+        else:
+            sup = pos & (inter.astype(np.float32) / np.where(pos, union, 1).astype(np.float32) > t32)
+        removed[i + 1 + cand[sup]] = True
+    return keep
