@@ -140,6 +140,60 @@ def large_window_pays(blur_dicts, n_images):
 LARGE_WINDOW_MAX_IMAGES = 2
 
 
+# ---- blur arithmetic (--blur_acc_mode) ------------------------------------------------------------------------
+# The ONE place that says what a mode means for a batch: the drivers' flag, engine._stage's compaction, blur_image_list,
+# manual_blur, blur_step and the estimator's engine all ask `resolve_acc_mode`.  Pure Python: no library, no GPU.
+ACC_MODES = {"bitexact": _lib.DIB_ACC_BITEXACT, "fp32": _lib.DIB_ACC_FP32, "fma16": _lib.DIB_ACC_FMA16, "fast16": _lib.DIB_ACC_FAST16}
+# stated distance from the bit-exact result on images in [0, 1] (tests/test_oracle_golden.py, tests/test_fast16_gpu.py)
+ACC_MODE_TOLERANCE = {"bitexact": 0.0, "fp32": 5e-3, "fma16": 1e-2, "fast16": 1e-2}
+_ACC_NAMES = {v: k for k, v in ACC_MODES.items()}
+
+
+def acc_mode_constant(mode):
+    """The library constant (DIB_ACC_*) of a mode given by name or by constant; ValueError for anything else."""
+    if isinstance(mode, str):
+        if mode not in ACC_MODES:
+            raise ValueError("unknown blur accumulation mode %r (one of %s)" % (mode, ", ".join(ACC_MODES)))
+        return ACC_MODES[mode]
+    if mode not in _ACC_NAMES:
+        raise ValueError("unknown blur accumulation mode %r (one of %s)" % (mode, ", ".join(ACC_MODES)))
+    return int(mode)
+
+
+class AccModeError(_lib.DibError, ValueError):
+    """A mode the images' dtype or the PSF canvas rules out, refused on the host in front of any launch.  The library's own refusal
+    (DIB_EINVAL: a DibError) and a ValueError at once: callers were promised either."""
+
+
+def resolve_acc_mode(mode, K, image_dtype, large_window=False, substitute=True):
+    """(mode by name or DIB_ACC_* constant, PSF canvas K, image dtype, was the large LDS window wanted)
+    -> (DIB_ACC_* constant to hand to the library, vruns, large_window): how the PSFs are to be compacted
+    (compact_psfs(vruns=, large_window=)) and what the blur is to be told.  `substitute` False: the caller names the very
+    arithmetic it wants (manual_blur's `acc_mode`, a library constant): where a batch path would run another mode in its place
+    (fast16 at K = 256) this is an AccModeError, as the library refuses it.
+      * The large window is a scheduling choice (large_window_pays: "never needed for correctness") that the library serves for
+        DIB_ACC_BITEXACT and DIB_ACC_FMA16 on fp16 images only: fp32 and fast16 always take the standard window.
+      * fast16 walks vertical-run groups, which exist on the 128 canvas only.  At K = 256 (--dont_center_psf) it runs
+        DIB_ACC_FMA16 instead: taps in row-major order, the same arithmetic class (fused multiply-add in fp16, within 1e-2) --
+        what the kernel itself does for a table without groups.
+      * fp32 at K = 256 is served as it is.
+      * fp32 images already accumulate in fp32: any mode but bitexact on them is an AccModeError (a ValueError), as in the library."""
+    if mode == _lib.DIB_ACC_BITEXACT and image_dtype is torch.float16:      # the default, on the host's hot path: nothing to decide
+        return _lib.DIB_ACC_BITEXACT, False, bool(large_window)
+    acc = acc_mode_constant(mode)
+    if image_dtype != torch.float16:
+        if acc != _lib.DIB_ACC_BITEXACT:
+            raise AccModeError(_lib.DIB_EINVAL, "blur accumulation mode %r applies to fp16 images only (%s images already accumulate in fp32)"
+                               % (_ACC_NAMES[acc], str(image_dtype).replace("torch.", "")))
+        return acc, False, False
+    if acc == _lib.DIB_ACC_FAST16 and K != 128:
+        if not substitute:
+            raise AccModeError(_lib.DIB_EINVAL, "blur accumulation mode 'fast16' serves the 128 canvas only (vertical-run groups), got K = %d" % K)
+        acc = _lib.DIB_ACC_FMA16
+    large = bool(large_window) and acc in (_lib.DIB_ACC_BITEXACT, _lib.DIB_ACC_FMA16)
+    return acc, acc == _lib.DIB_ACC_FAST16, large
+
+
 def compact_psfs(psfs, normalize, large_window=False, vruns=False):
     """psfs: list of K x K tensors (same K, same dtype) or one [B,K,K] tensor -> TapTables.
     A list is passed as device pointers (no stacking copy).  `large_window`: segment the taps for the large LDS window of
@@ -267,8 +321,8 @@ def sparse_blur(images, table_index, tables, acc_mode=_lib.DIB_ACC_BITEXACT):
 def sparse_blur_normalized(images, table_index, tables, means, stds, Hp, Wp, channels_last=False, acc_mode=_lib.DIB_ACC_BITEXACT, order=None):
     """sparse_blur + normalize_pad as ONE launch (dib_sparse_blur_normalized): the fp32 batch [B,3,Hp,Wp] holding
     (blurred - mean) / std inside each image and 0 in the padding, or None when the library does not serve the batch that way
-    (an image with table_index < 0, a padded extent the image's tiles do not cover, the large window, ...): the caller then
-    blurs and normalises in two launches.  images: 3 x H x W float16 CUDA tensors; means / stds: [B,3] rows.  `order`: the
+    (an image with table_index < 0, a padded extent the image's tiles do not cover, the large window, DIB_ACC_FAST16 at
+    K = 256, ...): the caller then blurs and normalises in two launches.  Every `acc_mode` of sparse_blur is served.  images: 3 x H x W float16 CUDA tensors; means / stds: [B,3] rows.  `order`: the
     sequence in which the images are handed to the launch (heaviest PSF first lets it end on its cheapest tiles); the batch
     position of every image stays its list position.  Bit-identical to the two launches."""
     import ctypes
@@ -282,6 +336,12 @@ def sparse_blur_normalized(images, table_index, tables, means, stds, Hp, Wp, cha
             return None
     if any(t < 0 for t in table_index):
         return None
+    if acc_mode == _lib.DIB_ACC_FAST16:
+        if tables.K != 128:
+            return None            # the vertical-run loop is K = 128 only: not served (the library answers the same)
+        if not tables.vruns:
+            raise ValueError("DIB_ACC_FAST16 walks the tables' vertical-run groups: compact with compact_psfs(..., vruns=True) "
+                             "(fp16 PSFs on the 128 canvas, standard window); without them the library would run DIB_ACC_FMA16's loop")
     _await(tables)
     seq = list(order) if order is not None else list(range(B))
     keep = [images[i] if images[i].is_contiguous() else images[i].contiguous() for i in seq]
@@ -393,8 +453,7 @@ def blur_step(images, table_index, psfs, normalize=True, acc_mode=_lib.DIB_ACC_B
             a = p.data_ptr()
             psfs_complete = False
         ptrs.append(a)
-    if large_window and (dt != torch.float16 or acc_mode == _lib.DIB_ACC_FP32):
-        large_window = False                # the large window serves the default fp16 tiles only
+    acc_mode, _vruns, large_window = resolve_acc_mode(acc_mode, K, dt, large_window)      # (the library compacts with the groups itself)
     flags = (_lib.DIB_STEP_PSFS_COMPLETE if psfs_complete else 0) | (_lib.DIB_STEP_LARGE_WINDOW if large_window else 0)
     l = _lib.lib()
     pa = _lib.ptr_array(ptrs + ins_p + outs_p)

@@ -1694,6 +1694,9 @@ int prepare_device() {
     DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>), QLDS_BYTES));
     DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 256>), QLDS_BYTES));
     DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 256>), QLDS_BYTES));
+    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FAST16, 128>), QLDS_BYTES));
+    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 128>), QLDS_BYTES));
+    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 256>), QLDS_BYTES));
     DIB_HIP_CHECK(opt_in((blur_quad_f32acc_kernel<128>), QLDS_BYTES));
     DIB_HIP_CHECK(opt_in((blur_quad_f32acc_kernel<256>), QLDS_BYTES));
     DIB_HIP_CHECK(opt_in((blur_step_f16_kernel<DIB_ACC_BITEXACT>), QLDS_BYTES + STEP_LDS_EXTRA));
@@ -1888,7 +1891,7 @@ int dib::blur_step_fused_launch(const void *const *psf_ptrs, int num_psfs, int n
   sy.sync = sync; sy.rec = rec; sy.target = target; sy.n_psf = num_psfs; sy.ncx = (num_psfs + 7) & ~7; sy.tables = tables;
   sy.row = sy.ncx + quad_grid_x(tiled);
   sy.poll_budget = g_poll_budget;
-  sy.flags = (normalize & ~DIB_COMPACT_LARGE_WINDOW) ? COMPACT_NORMALIZE : 0;
+  sy.flags = compact_wants_normalize(normalize) ? COMPACT_NORMALIZE : 0;
   { static const int skip = getenv("DIB_STEP_DEBUG_SKIP") ? 1 : 0; if (skip) sy.flags |= COMPACT_DEBUG_SKIP; }   // diagnostics: the hand-off alone
   if (g_step_nosignal) sy.flags |= COMPACT_DEBUG_NOSIGNAL;     // tests: a launch whose tables never arrive
   const dim3 grid(sy.row, tiled.n);
@@ -2032,9 +2035,10 @@ extern "C" int dib_sparse_blur_normalized(const void *const *in_dev, const int *
     return DIB_EINVAL;
   }
   if (K != 128 && K != 256) { set_error("dib_sparse_blur_normalized: K must be 128 or 256, got %d", K); return DIB_EINVAL; }
-  if (acc_mode != DIB_ACC_BITEXACT && acc_mode != DIB_ACC_FMA16) { set_error("dib_sparse_blur_normalized: DIB_ACC_BITEXACT or DIB_ACC_FMA16"); return DIB_EINVAL; }
+  if (acc_mode != DIB_ACC_BITEXACT && acc_mode != DIB_ACC_FP32 && acc_mode != DIB_ACC_FMA16 && acc_mode != DIB_ACC_FAST16) { set_error("dib_sparse_blur_normalized: unknown accumulation mode %d (the large window is not served: no DIB_WINDOW_LARGE)", acc_mode); return DIB_EINVAL; }
   if (Hp <= 0 || Wp <= 0 || (long long)Hp * Wp * 12 >= 0x7ffffff0ll) { set_error("dib_sparse_blur_normalized: bad padded size %d x %d", Hp, Wp); return DIB_EINVAL; }
   if (B > MAX_BATCH || g_shape != 0) return 1;
+  if (acc_mode == DIB_ACC_FAST16 && K != 128) return 1;      // the vertical-run loop is K = 128 only: the unfused path (there DIB_ACC_FMA16 serves K = 256)
   std::vector<int> C((size_t)B, 3);
   std::vector<void *> outs((size_t)B);
   for (int i = 0; i < B; ++i) {
@@ -2067,7 +2071,10 @@ extern "C" int dib_sparse_blur_normalized(const void *const *in_dev, const int *
   tiled.xcd_bands = 1;
   const dim3 grid(quad_grid_x(tiled), tiled.n);
   hipStream_t s = (hipStream_t)stream;
-  if (acc_mode == DIB_ACC_FMA16 && K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
+  if (acc_mode == DIB_ACC_FAST16) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FAST16, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
+  else if (acc_mode == DIB_ACC_FP32 && K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
+  else if (acc_mode == DIB_ACC_FP32) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
+  else if (acc_mode == DIB_ACC_FMA16 && K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
   else if (acc_mode == DIB_ACC_FMA16) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
   else if (K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
   else hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);

@@ -82,6 +82,9 @@ __device__ inline int map_coord(int s, int n, int pa, int pb, int mode, bool &ze
 }
 
 void set_error(const char *fmt, ...);
+// The `normalize` argument of the compaction entry points doubles as their flag word (include/dib.h): DIB_COMPACT_LARGE_WINDOW and
+// DIB_COMPACT_VRUNS are flags, anything else that is non-zero means "divide the PSF by its sum first".  Every launch decodes it here.
+inline bool compact_wants_normalize(int normalize) { return (normalize & ~(DIB_COMPACT_LARGE_WINDOW | DIB_COMPACT_VRUNS)) != 0; }
 // dib_compact.hip: the launch behind dib_psf_compact_list; any_order = hipExtAnyOrderLaunch (see dib_step.hip)
 int compact_launch(const void *const *ptrs, int dtype, int B, int K, int normalize, int *tables, hipStream_t s, bool any_order);
 // dib_blur.hip: compaction + blur as ONE launch (fp16 PSFs and images, K = 128, default tiles, at most MAX_BATCH of each).

@@ -260,7 +260,7 @@ int dib::compact_launch(const void *const *ptrs, int dtype, int B, int K, int no
     int *t = tables + (size_t)b0 * stride;
     // `normalize` doubles as the flag word: bit 3 (DIB_COMPACT_LARGE_WINDOW) selects the large-window segmentation, anything
     // else that is non-zero means "divide by the sum first"
-    const int flags = ((normalize & ~(DIB_COMPACT_LARGE_WINDOW | DIB_COMPACT_VRUNS)) ? COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? COMPACT_LARGE_WINDOW : 0) |
+    const int flags = (dib::compact_wants_normalize(normalize) ? COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? COMPACT_LARGE_WINDOW : 0) |
                       ((normalize & DIB_COMPACT_VRUNS) ? COMPACT_VRUNS : 0);
     if (dtype == DIB_F16 && K == 128) hipExtLaunchKernelGGL((dib::psf_compact_kernel<__half, 128>), dim3(n), dim3(dib::CT), 0, s, nullptr, nullptr, lflags, pp, flags, t);
     else if (dtype == DIB_F16) hipExtLaunchKernelGGL((dib::psf_compact_kernel<__half, 256>), dim3(n), dim3(dib::CT), 0, s, nullptr, nullptr, lflags, pp, flags, t);
@@ -310,7 +310,7 @@ extern "C" int dib_debug_compact_wg256(const void *const *psf_ptrs, int B, int n
   if (!psf_ptrs || !tables_dev || B < 1 || B > dib::MAX_BATCH) { dib::set_error("dib_debug_compact_wg256: bad arguments"); return DIB_EINVAL; }
   dib::PsfPtrs pp;
   for (int i = 0; i < B; ++i) pp.p[i] = psf_ptrs[i];
-  const int flags = ((normalize & ~DIB_COMPACT_LARGE_WINDOW) ? dib::COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? dib::COMPACT_LARGE_WINDOW : 0);
+  const int flags = (dib::compact_wants_normalize(normalize) ? dib::COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? dib::COMPACT_LARGE_WINDOW : 0);
   hipLaunchKernelGGL(dib::psf_compact_wg256_kernel, dim3(B), dim3(256), 19712, (hipStream_t)stream, pp, flags, (int *)tables_dev);
   DIB_HIP_CHECK(hipGetLastError());
   return DIB_OK;

@@ -22,24 +22,25 @@ from . import utils
 from .models import blur_functions, net_transforms
 
 
-def _to_device(images_CPU, targets, blur_dicts, device, blurring, want_tables=True, defer=False):
+def _to_device(images_CPU, targets, blur_dicts, device, blurring, want_tables=True, defer=False, blur_acc_mode="bitexact"):
     """reference engine.py:79-98: images as Half, PSFs via torch.HalfTensor(ndarray).
     Returns (images, targets, psfs, thetas, lambda1s, lambda2s, tables): `tables` are the batch's tap tables, being
     compacted on the side stream (None when nothing will consume them, on the CPU, or for PSFs of mixed shapes) --
     the caller hands them to `blur_image_list(tables=)` and `expand_targets(tables=)`.  `defer`: return (that tuple, event) and
     leave the hand-over to `_adopt` (the evaluation loop stages the NEXT batch while the detector runs on this one).
+    `blur_acc_mode` (--blur_acc_mode): the arithmetic the blur of this batch will run in -- it decides how the tables are compacted.
     On a GPU the whole batch is staged on the device's side stream: the fp32 tensors the DataLoader pinned are uploaded
     as they are (true asynchronous copies) and rounded to Half on the device -- the same round-to-nearest-even as
     `.half()` on the host -- while the main stream is still busy with the previous step; the main stream then waits for
     one event.  (Issued on the main stream, the 102 MB of a b = 8 batch at 800 x 1333 sit in front of the step: ~4 ms.)"""
     cuda = device.type == "cuda"
     if not cuda:
-        return _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, False)
+        return _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, False, blur_acc_mode)
     from . import blur_ops
     main = torch.cuda.current_stream(device)
     side = blur_ops.side_stream(device)
     with torch.cuda.stream(side):
-        out = _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, True)
+        out = _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, True, blur_acc_mode)
         staged = torch.cuda.Event()
         staged.record(side)
     if defer:
@@ -65,7 +66,7 @@ def _augmix_plan(blur_dict):
     return plan if plan is not None and plan["deferred"] else None
 
 
-def _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, cuda):
+def _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, cuda, blur_acc_mode="bitexact"):
     plans = [_augmix_plan(bd) for bd in blur_dicts]
     if cuda:
         uploaded = [image.to(device, non_blocking=True) for image in images_CPU]
@@ -106,9 +107,11 @@ def _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, cuda)
         if want_tables and cuda and active and len({tuple(p.shape) for p in active}) == 1 and active[0].dim() == 2 \
                 and active[0].shape[0] in (128, 256):
             from . import blur_ops
-            # fp16 images only (what the blur of this engine sees); the box growth reads the tap list, not the segments
-            large = blur_ops.large_window_pays(blur_dicts, len(active))
-            tables = blur_ops.compact_psfs_ahead(active, normalize=True, after_current=True, large_window=large)
+            # fp16 images only (what the blur of this engine sees); the box growth reads the tap list, not the segments or the
+            # vertical-run groups: boxes are the same in every mode
+            _acc, vruns, large = blur_ops.resolve_acc_mode(blur_acc_mode, active[0].shape[0], torch.float16,
+                                                           blur_ops.large_window_pays(blur_dicts, len(active)))
+            tables = blur_ops.compact_psfs_ahead(active, normalize=True, after_current=True, large_window=large, vruns=vruns)
         # theta / lambda1 / lambda2: one [3, B] pinned tensor, one copy
         scal = torch.tensor([[bd["theta_rad"] for bd in blur_dicts], [bd["scale_factor_lambda1"] for bd in blur_dicts],
                              [bd["scale_factor_lambda2"] for bd in blur_dicts]], dtype=torch.float16)
@@ -127,8 +130,9 @@ class _StagedAhead(object):
     tuple of `_to_device` (adopted by the main stream already); `may_prepare` False keeps (1) inline with the iteration (host
     random draws in `prepare`, the CPU)."""
 
-    def __init__(self, loader, device, blurring, want_tables, prepare, may_prepare=True):
+    def __init__(self, loader, device, blurring, want_tables, prepare, may_prepare=True, blur_acc_mode="bitexact"):
         self.it, self.device, self.blurring, self.want_tables = iter(loader), device, blurring, want_tables
+        self.blur_acc_mode = blur_acc_mode
         self.prepare, self.may_prepare = prepare, may_prepare and device.type == "cuda"
         self.staged, self.prepared, self.exhausted = [], None, False
 
@@ -142,7 +146,7 @@ class _StagedAhead(object):
             return
         images_CPU, targets_CPU, blur_dicts = batch
         self.staged.append((batch, _to_device(images_CPU, targets_CPU, blur_dicts, self.device, self.blurring, want_tables=self.want_tables,
-                                              defer=self.device.type == "cuda")))
+                                              defer=self.device.type == "cuda", blur_acc_mode=self.blur_acc_mode)))
 
     def _prepare_first(self):
         batch, staged = self.staged.pop(0)
@@ -208,7 +212,8 @@ FUSE_BLUR_EPILOGUE = os.environ.get("DIB_FUSE_BLUR_EPILOGUE") == "1"
 
 def _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, acc_mode=0):
     """Hands the batch's blur to the model's input transform (`pending_blur`, consumed by its next forward) instead of launching
-    it.  False when that path is not available (no fused transform, tables that do not belong to the batch)."""
+    it.  False when that path is not available (no fused transform, tables that do not belong to the batch).  `acc_mode`: the mode
+    asked for (a name or constant of blur_ops.ACC_MODES); the transform is handed what blur_ops.resolve_acc_mode makes of it."""
     tf = getattr(getattr(model, "module", model), "transform", None)
     if tf is None or not getattr(tf, "fused", False) or tables is None:
         return False
@@ -225,7 +230,9 @@ def _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, acc_mode=0):
         order = sorted(range(len(images_GPU)), key=lambda i: -int(blur_dicts[i]["psf_taps"]) if blur_dicts[i]["blurring"] else 1)
     except KeyError:
         pass
-    tf.pending_blur = (index, tables, acc_mode, order)
+    from . import blur_ops
+    acc, _vruns, _large = blur_ops.resolve_acc_mode(acc_mode, tables.K, images_GPU[idx[0]].dtype, tables.large)
+    tf.pending_blur = (index, tables, acc, order)
     return True
 
 
@@ -250,7 +257,10 @@ def _to_float(images_GPU, model, device):
 def train_one_epoch(model, optimizer, data_loader, device, epoch=0, print_freq=200, writer=None, distributed_mode=False,
                     blur_train=False, early_stop=False, gpu_blur=False, expand_target_boxes=False,
                     use_custom_image_norm=False, add_noise=False, noise_level=0.001, add_block=False,
-                    add_jpeg_artifact=False):
+                    add_jpeg_artifact=False, blur_acc_mode="bitexact"):
+    """`blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
+    from .blur_ops import acc_mode_constant
+    acc_mode = acc_mode_constant(blur_acc_mode)
     if writer is None:
         print("Warning! No tensorboard logger.")
     jpeg_compressor = None
@@ -282,15 +292,17 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch=0, print_freq=2
         guard = torch.empty(0)
     for images_CPU, targets, blur_dicts in metric_logger.log_every(data_loader, print_freq, header):
         images_GPU, targets_GPU, psfs_GPU, thetas, l1, l2, tables = _to_device(
-            images_CPU, targets, blur_dicts, device, blur_train, want_tables=gpu_blur or expand_target_boxes)
+            images_CPU, targets, blur_dicts, device, blur_train, want_tables=gpu_blur or expand_target_boxes,
+            blur_acc_mode=blur_acc_mode if gpu_blur else "bitexact")
         postponed = False
         if gpu_blur and blur_train:
             if FUSE_BLUR_EPILOGUE and not (add_noise or add_block or add_jpeg_artifact):
-                postponed = _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables)
+                postponed = _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, acc_mode)
             if not postponed:
                 blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, add_noise=add_noise,
                                                noise_level=noise_level, add_block=add_block,
-                                               add_jpeg_artifact=add_jpeg_artifact, jpeg_compressor=jpeg_compressor, tables=tables)
+                                               add_jpeg_artifact=add_jpeg_artifact, jpeg_compressor=jpeg_compressor, acc_mode=acc_mode,
+                                               tables=tables)
         if expand_target_boxes and blur_train:
             targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
         images_GPU = _to_float(images_GPU, model, device)
@@ -449,12 +461,15 @@ class EvaluationResult(object):
 def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None, vanilla_eval=False, blurring_images=False,
              gpu_blur=False, expand_target_boxes=False, deblur_first=False, deblurer=None, use_custom_image_norm=False,
              use_ensemble=False, ensemble_models=None, blur_estimator=None, add_noise=False, noise_level=0.001, add_block=False,
-             add_jpeg_artifact=False, image_output_folder=None, LEHE=False, epoch_number=None):
+             add_jpeg_artifact=False, image_output_folder=None, LEHE=False, epoch_number=None, blur_acc_mode="bitexact"):
     """reference engine.py:220-416.  Runs the detector (or the routed ensemble) over the loader, scores the
     detections against the dataset's COCO ground truth (boxes replaced by the expanded ones under
-    `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult)."""
+    `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
+    `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
+    from .blur_ops import acc_mode_constant
     from .coco_eval import CocoEvaluator
     from .coco_utils import get_coco_api_from_dataset
+    acc_mode = acc_mode_constant(blur_acc_mode)
     if deblur_first:
         raise NotImplementedError("--deblur_first is outside the built path (SURVEY.md section 2)")
     jpeg_compressor = None
@@ -505,7 +520,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             if gpu_blur and blurring_images:
                 blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, add_noise=add_noise, noise_level=noise_level,
                                                add_block=add_block, add_jpeg_artifact=add_jpeg_artifact,
-                                               jpeg_compressor=jpeg_compressor, tables=tables)
+                                               jpeg_compressor=jpeg_compressor, acc_mode=acc_mode, tables=tables)
             if expand_target_boxes and blurring_images:
                 targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
@@ -556,7 +571,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 in_flight = []
 
         ahead = _StagedAhead(metric_logger.log_every(data_loader, 100, "Test:"), device, blurring_images, gpu_blur or expand_target_boxes,
-                             prepare, may_prepare=not (add_noise or add_block or add_jpeg_artifact))
+                             prepare, may_prepare=not (add_noise or add_block or add_jpeg_artifact),
+                             blur_acc_mode=blur_acc_mode if gpu_blur else "bitexact")
         for _, (images_GPU, targets_GPU, blur_dicts, thetas, l1, l2, est) in ahead:
             if device.type == "cuda":
                 torch.cuda.synchronize()

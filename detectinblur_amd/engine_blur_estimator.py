@@ -18,7 +18,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import utils
+from . import _lib, utils
+from .blur_ops import acc_mode_constant
 from .models import blur_functions
 from .models.net_transforms import GeneralizedRCNNTransform
 
@@ -58,15 +59,17 @@ def accuracy(output, target, topk=(1,)):
 
 # ---- blur with the optional 800-px round trip ----------------------------------------------------------
 
-def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False):
+def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False, acc_mode=_lib.DIB_ACC_BITEXACT):
     """reference :69-79 around its private `manual_blur` (:27-67).  With resize_images every blurred image is first brought to
     height 800 (bilinear, aspect kept; a portrait image is transposed first and stays transposed), blurred, CROPPED to its
     ORIGINAL height x width from the top-left corner -- the reference takes `image_height` / `image_width` before the resize and
     crops the padded result with them (:29-30, :64) -- and that crop is interpolated to the original size (:66-72; a no-op
     resample unless the crop ran into the resized image's edge).  Pinned by tests/golden/detector_pins.json
-    (`estimator/*/blur_resize_quant`): the blur is the same HIP launch, on the resized image."""
+    (`estimator/*/blur_resize_quant`): the blur is the same HIP launch, on the resized image.
+    `acc_mode` (this repo, --blur_acc_mode): the blur's arithmetic, handed to that launch in both forms (what it means for the
+    batch's PSFs is decided there: blur_ops.resolve_acc_mode)."""
     if not resize_images:
-        return blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU)
+        return blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU, acc_mode=acc_mode)
     shapes, work = {}, list(images_GPU)
     for i, (img, bd) in enumerate(zip(images_GPU, blur_dicts)):
         if not bd["blurring"]:
@@ -80,7 +83,7 @@ def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False):
             new_w = int(800 * w / h)
         shapes[i] = (h, w)
         work[i] = F.interpolate(x, size=(800, new_w), mode="bilinear").squeeze(0)
-    blur_functions.blur_image_list(work, blur_dicts, psfs_GPU)
+    blur_functions.blur_image_list(work, blur_dicts, psfs_GPU, acc_mode=acc_mode)
     for i, (h, w) in shapes.items():
         crop = work[i][..., :h, :w]                     # `output[:, :, 63:63 + image_height, 63:63 + image_width]` of the padded result
         images_GPU[i] = F.interpolate(crop.unsqueeze(0), size=(h, w), mode="bilinear").squeeze()
@@ -132,9 +135,11 @@ def _targets(blur_dicts, device, LEHE_blur_seg):
 def train_one_epoch(model, optimizer, criterion, data_loader, device, print_freq=500, epoch=0, distributed_mode=False,
                     writer=None, gpu_blur=False, LEHE_blur_seg=False, resize_images=False, quantize_image=False,
                     crop_images=False, add_noise=False, noise_level=0.001, add_block=False, add_jpeg_artifact=False,
-                    early_stop=None, blur_train=False):
+                    early_stop=None, blur_train=False, blur_acc_mode="bitexact"):
     """reference :132-298, argument for argument.  Pinned against the reference's own function on a toy classifier
-    (oracle/gen_detector_pins.py -> tests/test_blur_estimator.py): weights, losses, label vectors, LR trajectory, scalars."""
+    (oracle/gen_detector_pins.py -> tests/test_blur_estimator.py): weights, losses, label vectors, LR trajectory, scalars.
+    `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
+    acc_mode = acc_mode_constant(blur_acc_mode)
     jpeg = _jpeg(device) if add_jpeg_artifact else None
     batcher = GeneralizedRCNNTransform(800, 1333, IMAGE_MEAN, IMAGE_STD, crop_images=crop_images)
     model.train()
@@ -148,7 +153,7 @@ def train_one_epoch(model, optimizer, criterion, data_loader, device, print_freq
         images, psfs = _stage(images_CPU, blur_dicts, device, blur_train)
         targets_dev = [{k: v.to(device) for k, v in t.items()} for t in targets]
         if gpu_blur and blur_train:
-            blur_image_list(images, blur_dicts, psfs, resize_images)
+            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode)
         images = _post(images, add_noise, noise_level, add_block, quantize_image, jpeg)
         batch = batcher([im.float() for im in images], targets_dev)[0].tensors
         target = _targets(blur_dicts, device, LEHE_blur_seg)
@@ -183,11 +188,13 @@ def train_one_epoch(model, optimizer, criterion, data_loader, device, print_freq
 @torch.no_grad()
 def evaluate(model, data_loader, device, distributed_mode=False, blurring_images=False, gpu_blur=False, LEHE_blur_seg=False,
              send_back_preds_targets=False, add_jpeg_artifact=False, resize_images=False, quantize_image=False,
-             add_noise=False, noise_level=0.001, add_block=False, early_stop=None):
+             add_noise=False, noise_level=0.001, add_block=False, early_stop=None, blur_acc_mode="bitexact"):
     """reference :301-492, argument for argument and return for return: `accuracies` = [top-1, top-2] in per cent over the images
     seen, or (accuracies, targetsAll, predsAll) with `send_back_preds_targets` -- the lists hold `target[0]` and `pred[0]` of
     every batch, as the reference's do (it evaluates with batch size 1, train_blur_estimator.py:206; with larger batches its
-    per-class summary fails on the stacked shapes, and so does this one).  Prints the reference's three summary lines."""
+    per-class summary fails on the stacked shapes, and so does this one).  Prints the reference's three summary lines.
+    `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
+    acc_mode = acc_mode_constant(blur_acc_mode)
     n_threads = torch.get_num_threads()
     jpeg = _jpeg(device) if add_jpeg_artifact else None
     batcher = GeneralizedRCNNTransform(800, 1333, IMAGE_MEAN, IMAGE_STD)
@@ -204,7 +211,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, blurring_images
         if gpu_blur:
             if psfs is None:      # the reference reads `psfs_GPU`, which only `blurring_images` assigns (:352-358, :361)
                 raise UnboundLocalError("local variable 'psfs_GPU' referenced before assignment")
-            blur_image_list(images, blur_dicts, psfs, resize_images)
+            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode)
         images = _post(images, add_noise, noise_level, add_block, quantize_image, jpeg)
         outputs = model(batcher([im.float() for im in images])[0].tensors)
         model_time = time.time() - model_time

@@ -126,7 +126,7 @@ def main(args):
             out = evaluate(model, loader_for(tf), device=device, distributed_mode=args.distributed, early_stop=args.early_stop,
                            blurring_images=True, gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                            use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
-                           add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, **ens_kw)
+                           add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode, **ens_kw)
             results["P%dE%d" % (param_index, fraction_index - 1)] = out
             if utils.is_main_process():
                 log_coco_stats(writer, "P" + str(param_index), out, fraction_index)

@@ -68,7 +68,9 @@ def manual_blur(image_GPU, psf_GPU, add_noise=False, noise_level=0.001, add_bloc
     _check_shapes(image_GPU, K)
     if psf_GPU.dtype != image_GPU.dtype:
         psf_GPU = psf_GPU.to(image_GPU.dtype)   # torch's `roll(image) * psf[r, c]` promotes a 0-dim tensor this way
-    tables = blur_ops.compact_psfs([psf_GPU], normalize=False, vruns=acc_mode == _lib.DIB_ACC_FAST16)
+    # `acc_mode` names the very arithmetic the caller wants: nothing is run in its place (blur_ops.resolve_acc_mode)
+    acc_mode, vruns, _ = blur_ops.resolve_acc_mode(acc_mode, K, image_GPU.dtype, substitute=False)
+    tables = blur_ops.compact_psfs([psf_GPU], normalize=False, vruns=vruns)
     out = blur_ops.sparse_blur([image_GPU], [0], tables, acc_mode)[0]
     out = out.squeeze()
     return _post_ops(out, add_noise, noise_level, add_block, add_jpeg_artifact, jpeg_compressor)
@@ -90,7 +92,10 @@ def blur_image_list(images_GPU, blur_dicts, psfs_GPU, add_noise=False, noise_lev
     `psfs_complete` (beyond the reference's signature as well): the caller states that the PSF tensors are complete when
     this call is made -- e.g. resident PSFs, or the reference's own `torch.HalfTensor(psf).to(device)` (engine.py:84: a
     synchronous copy) -- and not the product of kernels still queued on the current stream; the compaction then need not
-    wait for that stream and overlaps the previous batch's blur."""
+    wait for that stream and overlaps the previous batch's blur.
+    `acc_mode` (beyond it too): the arithmetic the caller asks for, a name or constant of blur_ops.ACC_MODES (--blur_acc_mode).
+    What runs is decided per group of PSFs by blur_ops.resolve_acc_mode: fast16 on the 256 canvas runs fma16, fp32 and fast16
+    never take the large window.  `tables` for fast16 must carry the vertical-run groups (compact_psfs_ahead(vruns=True))."""
     idx = [i for i, bd in enumerate(blur_dicts) if bd["blurring"]]
     if not idx:
         return None
@@ -155,9 +160,11 @@ def _blur_group(images_GPU, psfs_GPU, idx, acc_mode, blur_dicts=None, tables=Non
     if tables is None:
         large = (blur_dicts is not None and len(idx) <= blur_ops.LARGE_WINDOW_MAX_IMAGES
                  and blur_ops.large_window_pays([blur_dicts[i] for i in idx], len(idx)))
+        # (blur_step asks blur_ops.resolve_acc_mode what `acc_mode` means for these PSFs and whether `large` is served)
         outs = blur_ops.blur_step([images_GPU[idx[k]] for k in perm], perm, psfs, True, acc_mode, psfs_complete, large)
     else:
-        outs = blur_ops.sparse_blur([images_GPU[idx[k]] for k in perm], perm, tables, acc_mode)
+        acc, _vruns, _large = blur_ops.resolve_acc_mode(acc_mode, tables.K, images_GPU[idx[0]].dtype, tables.large)
+        outs = blur_ops.sparse_blur([images_GPU[idx[k]] for k in perm], perm, tables, acc)
     for j, k in enumerate(perm):
         o = outs[j]
         images_GPU[idx[k]] = o.squeeze() if 1 in o.shape else o       # reference :69 squeezes every unit dim

@@ -66,10 +66,36 @@ _OUT_OF_SCOPE = {"deblur_first": "the deblur-first pipeline (DeepDeblur)",
                  "blurred_dataset": "real-blur datasets (GOPRO / REDS)", "expand_synth_boxes": "real-blur datasets (GOPRO / REDS)"}
 
 
+BLUR_ACC_MODES = ("bitexact", "fp32", "fma16", "fast16")      # the keys of blur_ops.ACC_MODES (kept apart: parsers load no library code)
+
+
+def add_blur_acc_mode_flag(p):
+    p.add_argument("--blur_acc_mode", default="bitexact", choices=BLUR_ACC_MODES,
+                   help="(this repo) arithmetic of the --gpu_blur launch. bitexact: the reference's separately rounded fp16 multiply and add "
+                        "(default). fp32: fp32 accumulation, one rounding, within 5e-3 of bitexact. fma16: fused fp16 multiply-add, within "
+                        "1e-2. fast16: fma16's arithmetic over vertical runs of taps, the fastest, within 1e-2 (128 canvas; with "
+                        "--dont_center_psf it runs as fma16).")
+    return p
+
+
+def reject_idle_blur_acc_mode(args):
+    """A tolerance mode that no launch would run is refused at start, not silently ignored: only --gpu_blur reads the flag."""
+    mode = getattr(args, "blur_acc_mode", "bitexact")
+    if mode == "bitexact":
+        return
+    if getattr(args, "cpu_blur", False):
+        raise SystemExit("--blur_acc_mode %s with --cpu_blur: the mode is the arithmetic of the GPU blur launch and the loader's FFT blur "
+                         "never reads it; drop one of the two flags" % mode)
+    if not getattr(args, "gpu_blur", False):
+        raise SystemExit("--blur_acc_mode %s without --gpu_blur: the mode is the arithmetic of the GPU blur launch and would do nothing; "
+                         "add --gpu_blur or drop --blur_acc_mode" % mode)
+
+
 def reject_out_of_scope(args):
     for name, what in _OUT_OF_SCOPE.items():
         if getattr(args, name, False):
             raise SystemExit("--%s: %s is outside the built hot path (SURVEY.md section 2)" % (name, what))
+    reject_idle_blur_acc_mode(args)
     if getattr(args, "amp", False) and getattr(args, "mode_one_norm", False):
         raise SystemExit("--amp with --mode_one_norm: the test-time batch-norm kernel (dib_bn_mode_one_nhwc) and its tolerances are fp32; "
                          "drop one of the two flags")
@@ -106,6 +132,7 @@ def add_shared_flags(p):
     p.add_argument("--image_output_dir", default="debug", help="Output directory for images.")
     p.add_argument("--cpu_blur", action="store_true", help="CPU blurring in the Fourier domain, in the data loader's workers.")
     p.add_argument("--gpu_blur", action="store_true", help="GPU blurring, on the GPU in the training thread.")
+    add_blur_acc_mode_flag(p)
     p.add_argument("--param_index", default=None, help="Type of blur. Options are 1, 2, and 3.")
     p.add_argument("--high_exposure", action="store_true", help="Train and evaluate with high exposure blur.")
     p.add_argument("--low_exposure", action="store_true", help="Train and evaluate with low exposure blur.")
@@ -262,7 +289,7 @@ def main(args):
     blur_eval_kw = dict(device=device, early_stop=args.early_stop, distributed_mode=args.distributed, blurring_images=True,
                         gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                         use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
-                        add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts)
+                        add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode)
     # the clean pass takes none of the blur options (reference train.py:346-349)
     clean_kw = dict(device=device, distributed_mode=args.distributed, early_stop=args.early_stop, vanilla_eval=True)
     if args.eval_first:                                                 # :272-289
@@ -278,7 +305,7 @@ def main(args):
             train_sampler.set_epoch(epoch)
         train_one_epoch(model, optimizer, data_loader, device, epoch, args.print_freq, writer, args.distributed, args.blur_train,
                         args.early_stop, args.gpu_blur, args.expand_target_boxes, args.use_custom_image_norm, args.add_noise,
-                        args.noise_level, args.add_block, args.add_jpeg_artefacts)
+                        args.noise_level, args.add_block, args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode)
         lr_scheduler.step()
         if args.output_dir:
             utils.mkdir(args.output_dir)

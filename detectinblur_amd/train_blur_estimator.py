@@ -16,7 +16,7 @@ from . import utils
 from .coco_utils import get_coco
 from .engine_blur_estimator import evaluate, train_one_epoch
 from .models.blur_estimator import resnet18
-from .train import _seed_worker, get_transform, seed_everything
+from .train import _seed_worker, add_blur_acc_mode_flag, get_transform, reject_idle_blur_acc_mode, seed_everything
 
 
 def build_parser():
@@ -51,6 +51,7 @@ def build_parser():
     p.add_argument("--print_freq", default=20, type=int)
     p.add_argument("--blur_train", action="store_true")
     p.add_argument("--gpu_blur", action="store_true")
+    add_blur_acc_mode_flag(p)
     p.add_argument("--param_index", default=None)
     p.add_argument("--LEHE_blur_seg", action="store_true")
     p.add_argument("--high_exposure", action="store_true")
@@ -68,6 +69,7 @@ def build_parser():
 def main(args):
     from . import kernel_choices
     kernel_choices.use_shipped_kernel_choices()      # shipped MIOpen / TunableOp choices, private copy per process (kernel_choices.py)
+    reject_idle_blur_acc_mode(args)      # (this driver has no reject_out_of_scope: the same refusal, here)
     mp_ctx = utils.loader_context() if args.workers > 0 else None      # before anything touches the GPU (see utils.loader_context)
     utils.init_distributed_mode(args)
     print(args)
@@ -121,7 +123,7 @@ def main(args):
     eval_kw = dict(device=device, distributed_mode=args.distributed, blurring_images=True, gpu_blur=args.gpu_blur,
                    LEHE_blur_seg=args.LEHE_blur_seg, resize_images=args.resize_images, quantize_image=args.quantize_image,
                    add_noise=args.add_noise, noise_level=args.noise_level, add_block=args.add_block,
-                   add_jpeg_artifact=args.add_jpeg_artefacts, early_stop=args.early_stop)
+                   add_jpeg_artifact=args.add_jpeg_artefacts, early_stop=args.early_stop, blur_acc_mode=args.blur_acc_mode)
     if args.eval_first or args.test_only:
         evaluate(model, loader_test, **eval_kw)
         if args.test_only:
@@ -133,7 +135,8 @@ def main(args):
             train_sampler.set_epoch(epoch)
         train_one_epoch(model, optimizer, criterion, loader, device, args.print_freq, epoch, args.distributed, None,
                         args.gpu_blur, args.LEHE_blur_seg, args.resize_images, args.quantize_image, args.crop_images,
-                        args.add_noise, args.noise_level, args.add_block, args.add_jpeg_artefacts, args.early_stop, args.blur_train)
+                        args.add_noise, args.noise_level, args.add_block, args.add_jpeg_artefacts, args.early_stop, args.blur_train,
+                        blur_acc_mode=args.blur_acc_mode)
         scheduler.step()
         if args.output_dir:
             utils.mkdir(args.output_dir)

@@ -214,10 +214,14 @@ int dib_normalize_resize_pad(const void *const *in_dev, int dtype, const int *H,
  * image never has to exist).  in_dev: B device pointers to 3 x H[i] x W[i] fp16 images, table_index[i] >= 0 the table of
  * tables_dev image i uses; slot (may be NULL = identity): the batch position image i goes to (the caller may hand the images over
  * heaviest PSF first); mean / std: host [B][3] in the order of in_dev; out_dev: [B][3][Hp][Wp] fp32 planar or channels-last as
- * dib_normalize_pad, padding pixels are written as 0 by the launch.  acc_mode: DIB_ACC_BITEXACT or DIB_ACC_FMA16.
+ * dib_normalize_pad, padding pixels are written as 0 by the launch.  acc_mode: every mode dib_sparse_blur serves on the standard
+ * LDS window -- DIB_ACC_BITEXACT, DIB_ACC_FP32 (K = 128 and 256), DIB_ACC_FMA16, DIB_ACC_FAST16 (K = 128; on tables compacted without
+ * DIB_COMPACT_VRUNS it runs DIB_ACC_FMA16's row-major loop, as in dib_sparse_blur) -- without DIB_WINDOW_LARGE: the large window is
+ * not served here, tables compacted with DIB_COMPACT_LARGE_WINDOW go through dib_sparse_blur.
  * Returns DIB_OK, a negative error, or 1 = "not served, nothing launched" (an image that is not blurred, more than 32 images, a
- * padded extent the image's own tiles do not cover: Hp > ceil(H / 32) * 32 or Wp > ceil(W / 128) * 128): the caller then takes
- * the two-launch path.  Bit-identical to dib_sparse_blur followed by dib_normalize_pad. */
+ * padded extent the image's own tiles do not cover: Hp > ceil(H / 32) * 32 or Wp > ceil(W / 128) * 128, DIB_ACC_FAST16 at
+ * K = 256): the caller then takes the two-launch path.  Bit-identical to dib_sparse_blur in the same mode followed by
+ * dib_normalize_pad. */
 int dib_sparse_blur_normalized(const void *const *in_dev, const int *H, const int *W, const int *table_index, const int *slot, int B,
                                void *tables_dev, int num_tables, int K, int acc_mode, const float *mean, const float *std,
                                float *out_dev, int Hp, int Wp, int channels_last, void *stream);
