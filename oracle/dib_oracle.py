@@ -1069,3 +1069,229 @@ def nms_greedy(boxes, valid, thr):
             sup = pos & (inter.astype(np.float32) / np.where(pos, union, 1).astype(np.float32) > t32)
         removed[i + 1 + cand[sup]] = True
     return keep
+
+
+# --------------------------------------------------------------------------------------
+# A20 box matching, coding and detection candidates: float64 / int64 references for csrc/dib_detect.hip
+#     (torchvision's box_iou / Matcher / BoxCoder / RoIHeads.postprocess_detections up to the NMS, which reference
+#     models/faster_rcnn.py:150-159,198-229 configures)
+# --------------------------------------------------------------------------------------
+# Written from the published definitions in numpy float64 / int64, not from the kernels and without torch.  Boxes are
+# (x1, y1, x2, y2) float32 and are widened before the first operation.
+
+def _boxes64(b):
+    return np.asarray(b, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+
+
+def box_iou64(gt, cand):
+    """[G, 4] x [M, 4] -> [G, M] float64: inter / (area_a + area_b - inter) with the intersection's sides clamped at 0
+    and the areas unclamped (torchvision's box_iou); 0 / 0 is NaN."""
+    a, b = _boxes64(gt), _boxes64(cand)
+    lt = np.maximum(a[:, None, :2], b[None, :, :2])
+    rb = np.minimum(a[:, None, 2:], b[None, :, 2:])
+    wh = np.maximum(rb - lt, 0.0)
+    inter = wh[..., 0] * wh[..., 1]
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return inter / (area_a[:, None] + area_b[None, :] - inter)
+
+
+def _max_first(q, axis):
+    """(max, argmax) along `axis` as torch.max: the first index on ties (-0 == 0), the first NaN when there is one."""
+    nan = np.isnan(q)
+    has = nan.any(axis=axis)
+    arg = np.where(has, nan.argmax(axis=axis), np.where(nan, -np.inf, q).argmax(axis=axis))
+    return np.take_along_axis(q, np.expand_dims(arg, axis), axis).squeeze(axis), arg
+
+
+def match64(gt, cand, high, low, allow_low, guard=0.0):
+    """torchvision's Matcher on box_iou64 for one image: match [M] int64 -- the index of the ground truth of highest IoU,
+    -1 where that IoU is < low, -2 where it is in [low, high); with allow_low every candidate that attains some ground
+    truth's best IoU keeps its own argmax (a best of 0 restores every candidate with IoU 0).  No ground truth: -1.
+
+    guard == 0: the IoU is rounded once to float32 and the thresholds are np.float32(thr) -- for inputs whose areas,
+    intersections and unions are integers below 2^24 that is the float32 IoU of any correct implementation, and the
+    result is THE answer.  NaN (0 / 0) wins a candidate's maximum once and propagates into a ground truth's best, where
+    it equals nothing.
+
+    guard > 0: returns (match, accept [M, G + 2] bool -- accept[m, v + 2] says that answer v is acceptable --, near [M]).
+    Decisions are taken on the float64 IoU; an answer is acceptable when an IoU error below `guard` can produce it:
+    the maximum within guard of a threshold (both classes), a second ground truth within guard of the maximum (either
+    index), a candidate within guard of a ground truth's best without being its unique clear maximum (restored or
+    not).  Equal float64 IoUs of identical boxes, and IoUs that are exactly 0, are ties in float32 as well: the lowest
+    index / every such candidate is required, and they are not `near`."""
+    g32, c32 = np.asarray(gt, dtype=np.float32).reshape(-1, 4), np.asarray(cand, dtype=np.float32).reshape(-1, 4)
+    G, M = len(g32), len(c32)
+    lo, hi = float(np.float32(low)), float(np.float32(high))
+    if G == 0:
+        match = np.full(M, -1, dtype=np.int64)
+        if guard <= 0:
+            return match
+        accept = np.zeros((M, 2), dtype=bool)
+        accept[:, 1] = True
+        return match, accept, np.zeros(M, dtype=bool)
+    q = box_iou64(g32, c32)
+    if guard <= 0:
+        q = q.astype(np.float32).astype(np.float64)
+    cols = np.arange(M)
+    with np.errstate(invalid="ignore"):
+        vals, arg = _max_first(q, 0)
+        match = arg.astype(np.int64)
+        match[vals < lo] = -1
+        match[(vals >= lo) & (vals < hi)] = -2
+        if allow_low:
+            best, _ = _max_first(q, 1)
+            match = np.where((q == best[:, None]).any(axis=0), arg, match)
+        if guard <= 0:
+            return match
+        # ---- the acceptable set
+        has_nan = np.isnan(vals)
+        qq = np.where(np.isnan(q), -np.inf, q)
+        vmax = qq.max(axis=0)
+        S = qq >= vmax[None, :] - guard                               # indices a float32 argmax may return
+        same_gt = (g32[:, None, :] == g32[None, :, :]).all(axis=2)
+        for g in range(1, G):                                         # true ties: the lower index always wins
+            tie = S[:g] & (qq[:g] == qq[g][None, :]) & (same_gt[:g, g][:, None] | (qq[g] == 0)[None, :])
+            S[g] &= ~tie.any(axis=0)
+        S[:, has_nan] = False
+        S[arg[has_nan], cols[has_nan]] = True                         # 0 / 0 is NaN in any precision: decisive
+        multi = S.sum(axis=0) > 1
+        may_below = (vmax < lo + guard) & ~has_nan
+        may_between = (vmax >= lo - guard) & (vmax < hi + guard) & (hi > lo) & ~has_nan
+        may_match = (vmax >= hi - guard) | has_nan
+        sure = np.zeros(M, dtype=bool)
+        maybe = np.zeros(M, dtype=bool)
+        if allow_low:
+            bestq = np.where(np.isnan(best), np.inf, best)            # a NaN best equals nothing
+            T = qq >= bestq[:, None] - guard
+            first = T.argmax(axis=1)
+            same_c = (c32[None, :, :] == c32[first][:, None, :]).all(axis=2)
+            clean = ((~T | ((qq == bestq[:, None]) & (same_c | (bestq == 0)[:, None]))).all(axis=1)) & T.any(axis=1)
+            sure = (T & clean[:, None]).any(axis=0)
+            maybe = (T & ~clean[:, None]).any(axis=0) & ~sure
+        accept = np.zeros((M, G + 2), dtype=bool)
+        base_idx = may_match | sure | maybe
+        accept[:, 2:] = (S & base_idx[None, :]).T
+        accept[:, 1] = may_below & ~sure
+        accept[:, 0] = may_between & ~sure
+        n_class = may_below.astype(int) + may_between + may_match
+        near = maybe | (~sure & (n_class > 1)) | (multi & base_idx)
+    return match, accept, near
+
+
+def box_encode64(ref, cand, weights):
+    """R-CNN parameterisation of `ref` [M, 4] against `cand` [M, 4] in float64: (targets [M, 4], scale [M, 4]) with
+    dx = wx (gx - px) / pw, dw = ww log(gw / pw) (centres x + w / 2) and, per element, the magnitude a float32 rounding
+    error is relative to: wx (|gx| + |px|) / pw for the centres, ww (1 + |log(gw / pw)|) for the sizes."""
+    r, p = _boxes64(ref), _boxes64(cand)
+    wx, wy, ww, wh = [float(v) for v in weights]
+    out, scale = np.empty((len(p), 4)), np.empty((len(p), 4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k, (wc, ws) in enumerate(((wx, ww), (wy, wh))):
+            ps, gs = p[:, 2 + k] - p[:, k], r[:, 2 + k] - r[:, k]
+            pc, gc = p[:, k] + 0.5 * ps, r[:, k] + 0.5 * gs
+            out[:, k] = wc * (gc - pc) / ps
+            scale[:, k] = wc * (np.abs(gc) + np.abs(pc)) / np.abs(ps)
+            out[:, 2 + k] = ws * np.log(gs / ps)
+            scale[:, 2 + k] = ws * (1.0 + np.abs(np.log(gs / ps)))
+    return out, scale
+
+
+def _decode64(d, b, weights, clip):
+    """d [..., 4] deltas against b [..., 4] boxes (broadcast), float64 -> boxes, scale."""
+    wx, wy, ww, wh = [float(v) for v in weights]
+    out, scale = np.empty(d.shape), np.empty(d.shape)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k, (wc, ws) in enumerate(((wx, ww), (wy, wh))):
+            size = b[..., 2 + k] - b[..., k]
+            c = b[..., k] + 0.5 * size
+            dc, ds = d[..., k] / wc, d[..., 2 + k] / ws
+            ds = np.where(ds > clip, clip, ds)                        # min(dw, clip): NaN stays NaN
+            pc, ps = dc * size + c, np.exp(ds) * size
+            out[..., k], out[..., 2 + k] = pc - 0.5 * ps, pc + 0.5 * ps
+            s = np.abs(c) + np.abs(dc) * np.abs(size) + np.abs(ps) * (1.0 + np.abs(ds))
+            scale[..., k], scale[..., 2 + k] = s, s
+    return out, scale
+
+
+DECODE_CLIP = float(np.float32(math.log(1000.0 / 16)))
+
+
+def box_decode64(deltas, anchors, weights, clip=DECODE_CLIP):
+    """The inverse: deltas [R, 4] against anchors [A, 4] (row r uses anchor r % A) -> (boxes [R, 4], scale [R, 4]) in
+    float64, with true division by the weights and min(dw, clip), clip = float32(log(1000 / 16)) widened; the scale of
+    both corners of an axis is |cx| + |dx| w + pw (1 + |dw|)."""
+    d = np.asarray(deltas, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    a = _boxes64(anchors)
+    return _decode64(d, a[np.arange(len(d)) % len(a)], weights, float(clip))
+
+
+def det_candidates64(logits, deltas, rois, shape, weights, clip, score_thresh, min_size, c_score=0.0, c_box=0.0):
+    """One image's detection candidates before the NMS, class-major as the kernel writes them (class c in row c - 1):
+    logits [R, C], deltas [R, 4 C], rois [R, 4], shape (h, w) -> dict with
+      scores [C - 1, R] the float64 softmax,         sscale = score (1 + |x - max|) + 2^-126,
+      boxes [C - 1, R, 4] decoded and clipped,       bscale as box_decode64 (clipping is 1-Lipschitz),
+      kept: score > float32(score_thresh) and both sides >= float32(min_size),
+      near: the score is within c_score 2^-24 sscale of the threshold, or a side computed from corners that are each
+            off by up to c_box 2^-24 bscale (and then clipped) can fall on either side of min_size."""
+    x = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    R, C = x.shape
+    d = np.asarray(deltas, dtype=np.float32).astype(np.float64).reshape(R, C, 4)
+    m = x.max(axis=1, keepdims=True)
+    e = np.exp(x - m)
+    s = e / e.sum(axis=1, keepdims=True)
+    sscale = s * (1.0 + np.abs(x - m)) + 2.0 ** -126
+    raw, bscale = _decode64(d, _boxes64(rois)[:, None, :], weights, float(clip))
+    h, w = float(shape[0]), float(shape[1])
+    hi = np.array([w, h, w, h])
+
+    def clipped(v):
+        v = np.where(v < 0, 0.0, v)
+        return np.where(v > hi, hi, v)                                 # NaN stays NaN
+    boxes = clipped(raw)
+    thr, mins = float(np.float32(score_thresh)), float(np.float32(min_size))
+    u = 2.0 ** -24
+    with np.errstate(invalid="ignore"):
+        sides = boxes[..., 2:] - boxes[..., :2]
+        kept = (s > thr) & (sides >= mins).all(axis=-1)
+        eb = c_box * u * bscale
+        side_lo = clipped(raw - eb)[..., 2:] - clipped(raw + eb)[..., :2]
+        side_hi = clipped(raw + eb)[..., 2:] - clipped(raw - eb)[..., :2]
+        near_side = ((side_lo < mins) & (side_hi >= mins)).any(axis=-1)
+        near = (np.abs(s - thr) <= c_score * u * sscale) | near_side
+    cm = lambda a: np.ascontiguousarray(np.moveaxis(a[:, 1:], 0, 1))
+    return dict(scores=cm(s), sscale=cm(sscale), boxes=cm(boxes), bscale=cm(bscale), kept=cm(kept), near=cm(near))
+
+
+def pool64(props, gts, g_pad):
+    """box_pool_kernel: props [N, P, 4] -> [N, P + g_pad, 4] float32, image n's proposals, then its ground truth, then
+    [0, 0, 1, 1] rows."""
+    props = np.asarray(props, dtype=np.float32)
+    N, P = props.shape[:2]
+    out = np.empty((N, P + g_pad, 4), dtype=np.float32)
+    out[:, :P] = props
+    out[:, P:] = np.array([0, 0, 1, 1], dtype=np.float32)
+    for n, g in enumerate(gts):
+        assert len(g) <= g_pad
+        out[n, P:P + len(g)] = np.asarray(g, dtype=np.float32).reshape(-1, 4)
+    return out
+
+
+def labels64(match, gt_labels, ok, P):
+    """box_labels_kernel: match [N, M] int64 -> labels [N, M] int64: gt_labels[n][match] for match >= 0 (index clamped to
+    the image's last ground truth; 0 for an image without any), 0 for -1, -1 for -2; -1 on rows that are padding
+    (proposal rows j < P with ok[n, j] == 0, ground-truth rows j - P beyond the image's count)."""
+    match = np.asarray(match, dtype=np.int64)
+    N, M = match.shape
+    out = np.empty((N, M), dtype=np.int64)
+    j = np.arange(M)
+    for n in range(N):
+        lab = np.asarray(gt_labels[n], dtype=np.int64)
+        G = len(lab)
+        got = lab[np.clip(match[n], 0, G - 1)] if G else np.zeros(M, dtype=np.int64)
+        v = np.where(match[n] >= 0, got, np.where(match[n] == -1, 0, -1))
+        live = j - P < G
+        live[:P] = True if ok is None else np.asarray(ok)[n, :P] != 0
+        out[n] = np.where(live, v, -1)
+    return out
