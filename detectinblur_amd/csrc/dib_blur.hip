@@ -19,8 +19,8 @@
 //   default ("quad") shape  128 x 32 tile, lane = 32 h + j owns columns j + {0, 32, 64, 96} of 4 rows, 8-byte elements
 //                           {P[k], P[k+32] | P[k+64], P[k+96]}, 44 rows x 56 elements = 19.7 KB: 8 workgroups per CU
 //   256-wide shape          256 x 32 tile, lane owns columns l + 64k (k = 0..3) of 8 rows, 8-byte words, 44 x 96 words =
-//                           33.8 KB: 4 workgroups per CU; what DIB_ACC_FP32 runs on, and the second implementation the
-//                           tests compare with the default one bit for bit
+//                           33.8 KB: 4 workgroups per CU; only behind dib_debug_set_shape(1) / DIB_BLUR_SHAPE=1: the second
+//                           implementation the tests compare with the default one bit for bit, in every mode it serves
 //
 // What bounds it (measured: profiles/r2_blur_tap_slope.txt): a packed fp16 instruction occupies a SIMD for 4 cycles per
 // wave, and the bit-exact contract needs a multiply AND an add per 2 pixel-taps: 16.9 M wave-instructions for the BASELINE
@@ -29,7 +29,6 @@
 // eight of them per CU, and hence the instruction diet of everything outside the tap loop.
 #include "dib_compact_dev.h"
 #include <mutex>
-#include <vector>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1628,9 +1627,9 @@ extern "C" void dib_debug_set_stamp_buffer(void *dev_ptr) {
 #endif
 // Tile order of the tiled kernel: 1 = per-XCD bands (default), 0 = flat (the traffic experiment of DESIGN.md section 4).
 static int g_xcd_bands = 1;
-// Tile shape serving fp16 images in the bit-exact and FMA16 modes (all shapes bit-identical; tests/test_blur_gpu.py
-// compares them): 0 = 128 x 32 "quad" tiles (8-byte LDS elements), 8 workgroups per CU (default), 1 = 256 x 32 tiles,
-// 4 per CU (what DIB_ACC_FP32 always runs on: the second, independent tiled implementation).
+// Tile shape serving fp16 images (both shapes bit-identical in DIB_ACC_BITEXACT / FP32 / FMA16; tests/test_blur_gpu.py
+// compares them): 0 = 128 x 32 "quad" tiles (8-byte LDS elements), 8 workgroups per CU (default, every mode), 1 = 256 x 32 tiles,
+// 4 per CU (the second, independent tiled implementation; reached only through dib_debug_set_shape(1) / DIB_BLUR_SHAPE=1).
 static int shape_from_env() {   // DIB_BLUR_SHAPE=0|1 runs a whole test suite on one shape
   const char *e = getenv("DIB_BLUR_SHAPE");
   return e && e[0] == '1' && !e[1] ? 1 : 0;
@@ -1660,8 +1659,83 @@ struct DeviceState {
 std::mutex g_dev_mutex;
 DeviceState g_dev[64];
 
-template <typename Kern> hipError_t opt_in(Kern k, int bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// ---- which kernel serves what -------------------------------------------------------------------------------------------
+// The ONE list of this file's tiled instantiations, a family's dynamic-LDS size next to it: prepare_device opts in whatever the
+// selectors return, the entry points launch what the same selectors return.  nullptr = not served: the entry points refuse those
+// combinations in front of the selector (one that reaches `launch` is an internal error).  A new variant is one `case` here.
+constexpr int variant(int acc, int K, bool flat = false) { return (acc << 16) | (K << 1) | (flat ? 1 : 0); }
+constexpr int ALL_ACC[] = {DIB_ACC_BITEXACT, DIB_ACC_FP32, DIB_ACC_FMA16, DIB_ACC_FAST16};
+using QuadFn = void (*)(BlurBatch, FlatBands);
+using BatchFn = void (*)(BlurBatch);
+using NormFn = void (*)(BlurBatch, NormArgs);
+using StepFn = void (*)(BlurBatch, StepSync, PsfPtrs);
+using TiledFn = void (*)(BlurBatch, const int *, int, unsigned long long *);
+constexpr int QUAD_LDS = QLDS_BYTES + TL_EXTRA;        // default tiles, standard window; flat = the 1-D grid of a ragged batch
+QuadFn quad_kernel(int acc, int K, bool flat) {
+  switch (variant(acc, K, flat)) {
+    case variant(DIB_ACC_BITEXACT, 128): return blur_quad_f16_kernel<DIB_ACC_BITEXACT, 128>;
+    case variant(DIB_ACC_BITEXACT, 256): return blur_quad_f16_kernel<DIB_ACC_BITEXACT, 256>;
+    case variant(DIB_ACC_BITEXACT, 128, true): return blur_quad_f16_kernel<DIB_ACC_BITEXACT, 128, true>;
+    case variant(DIB_ACC_FMA16, 128): return blur_quad_f16_kernel<DIB_ACC_FMA16, 128>;
+    case variant(DIB_ACC_FMA16, 256): return blur_quad_f16_kernel<DIB_ACC_FMA16, 256>;
+    case variant(DIB_ACC_FMA16, 128, true): return blur_quad_f16_kernel<DIB_ACC_FMA16, 128, true>;
+    case variant(DIB_ACC_FAST16, 128): return blur_quad_f16_kernel<DIB_ACC_FAST16, 128>;
+    case variant(DIB_ACC_FAST16, 128, true): return blur_quad_f16_kernel<DIB_ACC_FAST16, 128, true>;
+    default: return nullptr;
+  }
+}
+constexpr int NORM_LDS = QLDS_BYTES;                   // blur + normalise + pad (dib_sparse_blur_normalized)
+NormFn norm_kernel(int acc, int K) {
+  switch (variant(acc, K)) {
+    case variant(DIB_ACC_BITEXACT, 128): return blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 128>;
+    case variant(DIB_ACC_BITEXACT, 256): return blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 256>;
+    case variant(DIB_ACC_FP32, 128): return blur_quad_f16_norm_kernel<DIB_ACC_FP32, 128>;
+    case variant(DIB_ACC_FP32, 256): return blur_quad_f16_norm_kernel<DIB_ACC_FP32, 256>;
+    case variant(DIB_ACC_FMA16, 128): return blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>;
+    case variant(DIB_ACC_FMA16, 256): return blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 256>;
+    case variant(DIB_ACC_FAST16, 128): return blur_quad_f16_norm_kernel<DIB_ACC_FAST16, 128>;
+    default: return nullptr;
+  }
+}
+constexpr int F32ACC_LDS = QLDS_BYTES;                 // DIB_ACC_FP32 on the default tiles
+BatchFn f32acc_kernel(int K) {
+  switch (K) { case 128: return blur_quad_f32acc_kernel<128>; case 256: return blur_quad_f32acc_kernel<256>; default: return nullptr; }
+}
+constexpr int LARGE_LDS = QGeom<true>::BYTES;          // default tiles, large window (DIB_WINDOW_LARGE)
+BatchFn large_kernel(int acc, int K) {
+  switch (variant(acc, K)) {
+    case variant(DIB_ACC_BITEXACT, 128): return blur_quad_large_f16_kernel<DIB_ACC_BITEXACT, 128>;
+    case variant(DIB_ACC_BITEXACT, 256): return blur_quad_large_f16_kernel<DIB_ACC_BITEXACT, 256>;
+    case variant(DIB_ACC_FMA16, 128): return blur_quad_large_f16_kernel<DIB_ACC_FMA16, 128>;
+    case variant(DIB_ACC_FMA16, 256): return blur_quad_large_f16_kernel<DIB_ACC_FMA16, 256>;
+    default: return nullptr;
+  }
+}
+constexpr int STEP_LDS = QLDS_BYTES + STEP_LDS_EXTRA;  // compaction + blur as one launch (K = 128)
+StepFn step_kernel(int acc) {
+  switch (acc) { case DIB_ACC_BITEXACT: return blur_step_f16_kernel<DIB_ACC_BITEXACT>; case DIB_ACC_FMA16: return blur_step_f16_kernel<DIB_ACC_FMA16>; default: return nullptr; }
+}
+constexpr int TILED_LDS = LDS_BYTES;                   // the 256-wide shape (any K)
+TiledFn tiled_kernel(int acc) {
+  switch (acc) {
+    case DIB_ACC_BITEXACT: return blur_tiled_f16_kernel<DIB_ACC_BITEXACT>;
+    case DIB_ACC_FP32: return blur_tiled_f16_kernel<DIB_ACC_FP32>;
+    case DIB_ACC_FMA16: return blur_tiled_f16_kernel<DIB_ACC_FMA16>;
+    default: return nullptr;
+  }
+}
+
+template <typename Kern> hipError_t opt_in(Kern k, int bytes) {      // (nullptr: not served, nothing to opt in)
+  return k ? hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess;
+}
+
+// The one launch site: 256 threads, the family's dynamic LDS.  Never launches a nullptr.
+template <typename... Args>
+int launch(const char *who, void (*kern)(Args...), dim3 grid, int lds_bytes, hipStream_t s, const Args &...args) {
+  if (!kern) { set_error("%s: internal error: no kernel serves this accumulation mode, K and grid", who); return DIB_EHIP; }
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, args...);
+  DIB_HIP_CHECK(hipGetLastError());
+  return DIB_OK;
 }
 
 int prepare_device() {
@@ -1679,32 +1753,17 @@ int prepare_device() {
       DIB_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(dib_status_word), &devp, sizeof(devp)));
       st.status = (volatile unsigned *)host;
     }
-    DIB_HIP_CHECK(opt_in(blur_tiled_f16_kernel<DIB_ACC_BITEXACT>, LDS_BYTES));
-    DIB_HIP_CHECK(opt_in(blur_tiled_f16_kernel<DIB_ACC_FP32>, LDS_BYTES));
-    DIB_HIP_CHECK(opt_in(blur_tiled_f16_kernel<DIB_ACC_FMA16>, LDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_BITEXACT, 128>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_FMA16, 128>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_BITEXACT, 128, true>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_FMA16, 128, true>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_FAST16, 128>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_FAST16, 128, true>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_BITEXACT, 256>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_kernel<DIB_ACC_FMA16, 256>), QLDS_BYTES + TL_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 128>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 256>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 256>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FAST16, 128>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 128>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 256>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f32acc_kernel<128>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_f32acc_kernel<256>), QLDS_BYTES));
-    DIB_HIP_CHECK(opt_in((blur_step_f16_kernel<DIB_ACC_BITEXACT>), QLDS_BYTES + STEP_LDS_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_step_f16_kernel<DIB_ACC_FMA16>), QLDS_BYTES + STEP_LDS_EXTRA));
-    DIB_HIP_CHECK(opt_in((blur_quad_large_f16_kernel<DIB_ACC_BITEXACT, 128>), QGeom<true>::BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_large_f16_kernel<DIB_ACC_FMA16, 128>), QGeom<true>::BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_large_f16_kernel<DIB_ACC_BITEXACT, 256>), QGeom<true>::BYTES));
-    DIB_HIP_CHECK(opt_in((blur_quad_large_f16_kernel<DIB_ACC_FMA16, 256>), QGeom<true>::BYTES));
+    for (int acc : ALL_ACC) {
+      DIB_HIP_CHECK(opt_in(tiled_kernel(acc), TILED_LDS));
+      DIB_HIP_CHECK(opt_in(step_kernel(acc), STEP_LDS));
+      for (int K : {128, 256}) {
+        DIB_HIP_CHECK(opt_in(quad_kernel(acc, K, false), QUAD_LDS));
+        DIB_HIP_CHECK(opt_in(quad_kernel(acc, K, true), QUAD_LDS));
+        DIB_HIP_CHECK(opt_in(norm_kernel(acc, K), NORM_LDS));
+        DIB_HIP_CHECK(opt_in(large_kernel(acc, K), LARGE_LDS));
+      }
+    }
+    for (int K : {128, 256}) DIB_HIP_CHECK(opt_in(f32acc_kernel(K), F32ACC_LDS));
     st.ready = true;
   }
   return DIB_OK;
@@ -1813,32 +1872,69 @@ int check_images(const void *const *in_dev, void *const *out_dev, const int *C, 
   return DIB_OK;
 }
 
-// Descriptor of image i for the default ("quad") tiles.
-ImageDesc quad_desc(const void *in, void *out, int C, int H, int W, int table, const int *tables, int K, int tile_begin) {
-  ImageDesc d;
-  d.in = in; d.out = out; d.C = C; d.H = H; d.W = W; d.table = table;
-  d.tiles_x = (W + QTILE_W - 1) / QTILE_W;
-  d.tiles_y = (H + TH - 1) / TH;
-  d.inv_per_ch = magic_inverse((unsigned)(d.tiles_x * d.tiles_y));
-  d.inv_tiles_x = magic_inverse((unsigned)d.tiles_x);
-  d.tab = tables + (size_t)table * table_words(K);
-  d.tile_begin = tile_begin;
-  return d;
+// The 8 per-XCD bands T tiles are dealt into: band x holds tiles [(x * T) >> 3, ((x + 1) * T) >> 3) (band_entry above)
+int band_length(int T, int x) { return (((x + 1) * T) >> 3) - ((x * T) >> 3); }
+// the longest of them: every band is T / 8 rounded down or up, and they add up to T
+int longest_band(int T) { return (T + 7) >> 3; }
+
+// The launch descriptor of the images [first, B) that are to be blurred (table_index >= 0), MAX_BATCH of them at most, cut into
+// tiles tile_w wide (QTILE_W: the default "quad" tiles, TILE_W: the 256-wide shape).  Returns the image the next launch starts at.
+int build_batch(BlurBatch &b, int tile_w, int xcd_bands, const void *const *in_dev, void *const *out_dev, const int *C, const int *H,
+                const int *W, const int *table_index, int first, int B, const int *tables, int K) {
+  int i = first, tiles = 0;
+  b.n = 0;
+  for (; i < B && b.n < MAX_BATCH; ++i) {
+    if (table_index[i] < 0) continue;
+    ImageDesc d;
+    d.in = in_dev[i]; d.out = out_dev[i]; d.C = C[i]; d.H = H[i]; d.W = W[i]; d.table = table_index[i];
+    d.tiles_x = (W[i] + tile_w - 1) / tile_w;
+    d.tiles_y = (H[i] + TH - 1) / TH;
+    d.inv_per_ch = magic_inverse((unsigned)(d.tiles_x * d.tiles_y));
+    d.inv_tiles_x = magic_inverse((unsigned)d.tiles_x);
+    d.tab = tables + (size_t)table_index[i] * table_words(K);
+    d.tile_begin = b.tile_begin[b.n] = tiles;
+    tiles += d.C * d.tiles_x * d.tiles_y;
+    b.img[b.n++] = d;
+  }
+  for (int k = b.n; k <= MAX_BATCH; ++k) b.tile_begin[k] = tiles;
+  b.total_tiles = tiles;
+  b.xcd_bands = xcd_bands;
+  return i;
 }
 
-// x extent of the quad grid: 8 x the longest per-XCD band of the launch's images
-int quad_grid_x(const BlurBatch &b) {
+// x extent of the 2-D grid (y = image): the launch's longest image -- 8 x its longest band, or (flat tile order) its tile count
+int grid_x(const BlurBatch &b, bool banded = true) {
   int gx = 0;
   for (int k = 0; k < b.n; ++k) {
-    const int T = b.img[k].C * b.img[k].tiles_x * b.img[k].tiles_y;
-    int longest = 0;
-    for (int x = 0; x < 8; ++x) {
-      const int len = (((x + 1) * T) >> 3) - ((x * T) >> 3);
-      longest = len > longest ? len : longest;
-    }
-    gx = 8 * longest > gx ? 8 * longest : gx;
+    const int T = b.tile_begin[k + 1] - b.tile_begin[k];
+    const int ext = banded ? 8 * longest_band(T) : T;
+    gx = ext > gx ? ext : gx;
   }
   return gx;
+}
+
+// Ragged batch on the default tiles: a 1-D grid of exactly the working workgroups (FlatBands, dib_common.h).  Fills `fb` and
+// returns the grid's x extent, or 0 for a batch that stays on the 2-D grid (one image, more than FLAT_MAX, all of one tile count).
+int flat_grid_x(const BlurBatch &b, int acc_mode, FlatBands &fb) {
+  if (!g_flat_grid || b.n < 2 || b.n > FLAT_MAX) return 0;
+  bool ragged = false;
+  for (int k = 1; k < b.n && !ragged; ++k) ragged = b.tile_begin[k + 1] - b.tile_begin[k] != b.tile_begin[1] - b.tile_begin[0];
+  if (!ragged) return 0;
+  int longest = 0;
+  for (int x = 0; x < 8; ++x) {
+    int at = 0;
+    for (int k = 0; k < 16; ++k) {
+      fb.begin[x][k] = k < b.n ? at : 0x7fffffff;
+      if (k < b.n) at += band_length(b.tile_begin[k + 1] - b.tile_begin[k], x);
+    }
+    fb.begin[x][15] = at;
+    longest = at > longest ? at : longest;
+  }
+  // strides walked backwards: all of them in the bit-exact mode (the kernel's comment; only FULL strides are looked at), none in
+  // the tolerance modes, whose launch is not bound by a CU's vector-ALU work (profiles/r6_native_order.txt: 12.5 us straight,
+  // 12.8 reversed); A/B runs set the mask
+  fb.rev_mask = g_flat_mask >= 0 ? (unsigned)g_flat_mask : (g_flat_snake && acc_mode == DIB_ACC_BITEXACT ? 0xffffffffu : 0u);
+  return 8 * longest;
 }
 }  // namespace
 
@@ -1853,7 +1949,7 @@ extern "C" void dib_debug_set_step_fused(int on) { g_step_fused = on ? 1 : 0; }
 int dib::blur_step_fused_launch(const void *const *psf_ptrs, int num_psfs, int normalize, const void *const *in_dev, void *const *out_dev,
                                 const int *C, const int *H, const int *W, const int *table_index, int B, int acc_mode, int *tables,
                                 unsigned *sync, unsigned *rec, unsigned target, hipStream_t s) {
-  if (!g_step_fused || g_shape != 0 || num_psfs > MAX_BATCH || (acc_mode != DIB_ACC_BITEXACT && acc_mode != DIB_ACC_FMA16)) return 1;
+  if (!g_step_fused || g_shape != 0 || num_psfs > MAX_BATCH || !step_kernel(acc_mode)) return 1;
   if (B < 0 || (B > 0 && (!in_dev || !out_dev || !C || !H || !W || !table_index))) {
     set_error("dib_blur_step: null pointer or negative batch");
     return DIB_EINVAL;
@@ -1875,30 +1971,15 @@ int dib::blur_step_fused_launch(const void *const *psf_ptrs, int num_psfs, int n
     if (g_dev[dev].step_single_off) return 1;
   }
   BlurBatch tiled;
-  tiled.n = 0;
-  int tiles = 0;
-  for (int i = 0; i < B; ++i) {
-    if (table_index[i] < 0) continue;
-    const ImageDesc d = quad_desc(in_dev[i], out_dev[i], C[i], H[i], W[i], table_index[i], tables, 128, tiles);
-    tiled.tile_begin[tiled.n] = tiles;
-    tiles += d.C * d.tiles_x * d.tiles_y;
-    tiled.img[tiled.n++] = d;
-  }
-  for (int k = tiled.n; k <= MAX_BATCH; ++k) tiled.tile_begin[k] = tiles;
-  tiled.total_tiles = tiles;
-  tiled.xcd_bands = 1;
+  build_batch(tiled, QTILE_W, 1, in_dev, out_dev, C, H, W, table_index, 0, B, tables, 128);
   StepSync sy;
   sy.sync = sync; sy.rec = rec; sy.target = target; sy.n_psf = num_psfs; sy.ncx = (num_psfs + 7) & ~7; sy.tables = tables;
-  sy.row = sy.ncx + quad_grid_x(tiled);
+  sy.row = sy.ncx + grid_x(tiled);
   sy.poll_budget = g_poll_budget;
-  sy.flags = compact_wants_normalize(normalize) ? COMPACT_NORMALIZE : 0;
+  sy.flags = compact_kernel_flags(normalize);   // (no large window, no vertical runs: dib_step.hip sends neither here)
   { static const int skip = getenv("DIB_STEP_DEBUG_SKIP") ? 1 : 0; if (skip) sy.flags |= COMPACT_DEBUG_SKIP; }   // diagnostics: the hand-off alone
   if (g_step_nosignal) sy.flags |= COMPACT_DEBUG_NOSIGNAL;     // tests: a launch whose tables never arrive
-  const dim3 grid(sy.row, tiled.n);
-  if (acc_mode == DIB_ACC_FMA16) hipLaunchKernelGGL((blur_step_f16_kernel<DIB_ACC_FMA16>), grid, dim3(256), QLDS_BYTES + STEP_LDS_EXTRA, s, tiled, sy, pp);
-  else hipLaunchKernelGGL((blur_step_f16_kernel<DIB_ACC_BITEXACT>), grid, dim3(256), QLDS_BYTES + STEP_LDS_EXTRA, s, tiled, sy, pp);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return launch("dib_blur_step", step_kernel(acc_mode), dim3(sy.row, tiled.n), STEP_LDS, s, tiled, sy, pp);
 }
 
 extern "C" int dib_sparse_blur(const void *const *in_dev, void *const *out_dev, const int *C, const int *H,
@@ -1926,103 +2007,33 @@ extern "C" int dib_sparse_blur(const void *const *in_dev, void *const *out_dev, 
   hipStream_t s = (hipStream_t)stream;
   if (int rc = prepare_device()) return rc;
   if (int rc = consume_device_status("dib_sparse_blur")) return rc;
-  int i = 0;
-  while (i < B) {
-    BlurBatch tiled, generic;
-    const bool quad = g_shape == 0 && dtype == DIB_F16;
-    tiled.n = generic.n = 0;
-    int tiles = 0, gblocks = 0;
-    for (; i < B && tiled.n < MAX_BATCH; ++i) {
-      if (table_index[i] < 0) continue;
-      ImageDesc d;
-      d.in = in_dev[i]; d.out = out_dev[i]; d.C = C[i]; d.H = H[i]; d.W = W[i]; d.table = table_index[i];
-      d.tiles_x = quad ? (W[i] + QTILE_W - 1) / QTILE_W : (W[i] + TILE_W - 1) / TILE_W;
-      d.tiles_y = (H[i] + TH - 1) / TH;
-      d.inv_per_ch = magic_inverse((unsigned)(d.tiles_x * d.tiles_y));
-      d.inv_tiles_x = magic_inverse((unsigned)d.tiles_x);
-      d.tab = (const int *)tables_dev + (size_t)table_index[i] * table_words(K);
-      d.tile_begin = tiles;
-      tiled.tile_begin[tiled.n] = tiles;
-      tiles += d.C * d.tiles_x * d.tiles_y;
-      tiled.img[tiled.n++] = d;
-      long long n = (long long)C[i] * H[i] * W[i];
-      d.tile_begin = gblocks;
-      gblocks += (int)((n + 255) / 256);
-      generic.img[generic.n++] = d;
-    }
-    if (tiled.n == 0) break;
-    tiled.total_tiles = tiles;
-    generic.total_tiles = gblocks;
-    tiled.xcd_bands = g_xcd_bands;
-    generic.xcd_bands = 0;
-    if (dtype == DIB_F16) {
-      for (int k = tiled.n; k <= MAX_BATCH; ++k) tiled.tile_begin[k] = tiles;
-      // x extent: the longest image of the launch -- 8 x its longest band, or (flat order) its tile count
-      int gx = 0;
-      for (int k = 0; k < tiled.n; ++k) {
-        const int T = tiled.tile_begin[k + 1] - tiled.tile_begin[k];
-        int ext = T;
-        if (g_xcd_bands || quad) {
-          int longest = 0;
-          for (int x = 0; x < 8; ++x) {
-            const int len = (((x + 1) * T) >> 3) - ((x * T) >> 3);
-            longest = len > longest ? len : longest;
-          }
-          ext = 8 * longest;
-        }
-        gx = ext > gx ? ext : gx;
+  const int *tables = (const int *)tables_dev;
+  const bool quad = g_shape == 0 && dtype == DIB_F16;
+  for (int i = 0; i < B;) {
+    BlurBatch batch;
+    i = build_batch(batch, quad ? QTILE_W : TILE_W, g_xcd_bands, in_dev, out_dev, C, H, W, table_index, i, B, tables, K);
+    if (batch.n == 0) break;
+    int rc;
+    if (dtype == DIB_F32) {      // the generic kernel: one block per 256 elements, tile_begin = an image's first block
+      int blocks = 0;
+      for (int k = 0; k < batch.n; ++k) {
+        batch.img[k].tile_begin = blocks;
+        blocks += (int)(((long long)batch.img[k].C * batch.img[k].H * batch.img[k].W + 255) / 256);
       }
-      dim3 grid(gx, tiled.n);
-      // ragged batch on the default tiles: a 1-D grid of exactly the working workgroups (FlatBands, dib_common.h)
-      FlatBands fb = {};
-      bool flat = false;
-      if (quad && !large && K == 128 && g_flat_grid && tiled.n > 1 && tiled.n <= FLAT_MAX && acc_mode != DIB_ACC_FP32) {    // (FAST16 included)
-        for (int k = 1; k < tiled.n && !flat; ++k)
-          flat = tiled.tile_begin[k + 1] - tiled.tile_begin[k] != tiled.tile_begin[1] - tiled.tile_begin[0];
-        if (flat) {
-          int longest = 0;
-          for (int x = 0; x < 8; ++x) {
-            int at = 0;
-            for (int k = 0; k < 16; ++k) {
-              fb.begin[x][k] = k < tiled.n ? at : 0x7fffffff;
-              if (k < tiled.n) {
-                const int T = tiled.tile_begin[k + 1] - tiled.tile_begin[k];
-                at += (((x + 1) * T) >> 3) - ((x * T) >> 3);
-              }
-            }
-            fb.begin[x][15] = at;
-            longest = at > longest ? at : longest;
-          }
-          grid = dim3(8 * longest, 1);
-          // strides walked backwards: all of them in the bit-exact mode (the kernel's comment; only FULL strides are looked at), none in
-          // the tolerance modes, whose launch is not bound by a CU's vector-ALU work (profiles/r6_native_order.txt: 12.5 us straight,
-          // 12.8 reversed); A/B runs set the mask
-          fb.rev_mask = g_flat_mask >= 0 ? (unsigned)g_flat_mask : (g_flat_snake && acc_mode == DIB_ACC_BITEXACT ? 0xffffffffu : 0u);
-        }
-      }
-#define DIB_LAUNCH_QUAD(ACCM)                                                                                             \
-  do {                                                                                                                   \
-    if (large && K == 128) hipLaunchKernelGGL((blur_quad_large_f16_kernel<ACCM, 128>), grid, dim3(256), QGeom<true>::BYTES, s, tiled); \
-    else if (large) hipLaunchKernelGGL((blur_quad_large_f16_kernel<ACCM, 256>), grid, dim3(256), QGeom<true>::BYTES, s, tiled);       \
-    else if (flat) hipLaunchKernelGGL((blur_quad_f16_kernel<ACCM, 128, true>), grid, dim3(256), QLDS_BYTES + TL_EXTRA, s, tiled, fb); \
-    else if (K == 128) hipLaunchKernelGGL((blur_quad_f16_kernel<ACCM, 128>), grid, dim3(256), QLDS_BYTES + TL_EXTRA, s, tiled, fb); \
-    else hipLaunchKernelGGL((blur_quad_f16_kernel<ACCM, 256>), grid, dim3(256), QLDS_BYTES + TL_EXTRA, s, tiled, fb);          \
-  } while (0)
-      if (quad && acc_mode == DIB_ACC_FAST16) {
-        if (flat) hipLaunchKernelGGL((blur_quad_f16_kernel<DIB_ACC_FAST16, 128, true>), grid, dim3(256), QLDS_BYTES + TL_EXTRA, s, tiled, fb);
-        else hipLaunchKernelGGL((blur_quad_f16_kernel<DIB_ACC_FAST16, 128>), grid, dim3(256), QLDS_BYTES + TL_EXTRA, s, tiled, fb);
-      } else if (quad && acc_mode == DIB_ACC_FMA16) DIB_LAUNCH_QUAD(DIB_ACC_FMA16);
-      else if (quad && acc_mode == DIB_ACC_FP32 && K == 128) hipLaunchKernelGGL((blur_quad_f32acc_kernel<128>), grid, dim3(256), QLDS_BYTES, s, tiled);
-      else if (quad && acc_mode == DIB_ACC_FP32) hipLaunchKernelGGL((blur_quad_f32acc_kernel<256>), grid, dim3(256), QLDS_BYTES, s, tiled);
-      else if (quad) DIB_LAUNCH_QUAD(DIB_ACC_BITEXACT);
-#undef DIB_LAUNCH_QUAD
-      else if (acc_mode == DIB_ACC_FP32) hipLaunchKernelGGL((blur_tiled_f16_kernel<DIB_ACC_FP32>), grid, dim3(256), LDS_BYTES, s, tiled, (const int *)tables_dev, K, g_stamp_buffer);
-      else if (acc_mode == DIB_ACC_FMA16) hipLaunchKernelGGL((blur_tiled_f16_kernel<DIB_ACC_FMA16>), grid, dim3(256), LDS_BYTES, s, tiled, (const int *)tables_dev, K, g_stamp_buffer);
-      else hipLaunchKernelGGL((blur_tiled_f16_kernel<DIB_ACC_BITEXACT>), grid, dim3(256), LDS_BYTES, s, tiled, (const int *)tables_dev, K, g_stamp_buffer);
+      batch.total_tiles = blocks;
+      batch.xcd_bands = 0;
+      rc = launch("dib_sparse_blur", blur_generic_kernel<float, DIB_ACC_BITEXACT>, dim3(blocks), 0, s, batch, tables, K);
     } else {
-      hipLaunchKernelGGL((blur_generic_kernel<float, DIB_ACC_BITEXACT>), dim3(gblocks), dim3(256), 0, s, generic, (const int *)tables_dev, K);
+      const dim3 grid(grid_x(batch, g_xcd_bands || quad), batch.n);
+      FlatBands fb = {};
+      if (!quad) rc = launch("dib_sparse_blur", tiled_kernel(acc_mode), grid, TILED_LDS, s, batch, tables, K, g_stamp_buffer);
+      else if (large) rc = launch("dib_sparse_blur", large_kernel(acc_mode, K), grid, LARGE_LDS, s, batch);
+      else if (acc_mode == DIB_ACC_FP32) rc = launch("dib_sparse_blur", f32acc_kernel(K), grid, F32ACC_LDS, s, batch);
+      else if (const int flat_x = K == 128 ? flat_grid_x(batch, acc_mode, fb) : 0)
+        rc = launch("dib_sparse_blur", quad_kernel(acc_mode, K, true), dim3(flat_x), QUAD_LDS, s, batch, fb);
+      else rc = launch("dib_sparse_blur", quad_kernel(acc_mode, K, false), grid, QUAD_LDS, s, batch, fb);
     }
-    DIB_HIP_CHECK(hipGetLastError());
+    if (rc) return rc;
   }
   return DIB_OK;
 }
@@ -2039,47 +2050,28 @@ extern "C" int dib_sparse_blur_normalized(const void *const *in_dev, const int *
   if (Hp <= 0 || Wp <= 0 || (long long)Hp * Wp * 12 >= 0x7ffffff0ll) { set_error("dib_sparse_blur_normalized: bad padded size %d x %d", Hp, Wp); return DIB_EINVAL; }
   if (B > MAX_BATCH || g_shape != 0) return 1;
   if (acc_mode == DIB_ACC_FAST16 && K != 128) return 1;      // the vertical-run loop is K = 128 only: the unfused path (there DIB_ACC_FMA16 serves K = 256)
-  std::vector<int> C((size_t)B, 3);
-  std::vector<void *> outs((size_t)B);
+  int C[MAX_BATCH];
+  void *outs[MAX_BATCH];
+  NormArgs na;
+  na.Hp = Hp; na.Wp = Wp; na.nhwc = channels_last ? 1 : 0;
   for (int i = 0; i < B; ++i) {
     const int sl = slot ? slot[i] : i;
     if (sl < 0 || sl >= B) { set_error("dib_sparse_blur_normalized: slot[%d] = %d out of range", i, sl); return DIB_EINVAL; }
+    C[i] = 3;
     outs[i] = out_dev + (size_t)sl * 3 * Hp * Wp;
     if (table_index[i] < 0) return 1;                                         // an image that is not blurred: the unfused path
     if (H[i] > Hp || W[i] > Wp) { set_error("dib_sparse_blur_normalized: image %d (%d x %d) exceeds the batch (%d x %d)", i, H[i], W[i], Hp, Wp); return DIB_EINVAL; }
     // the padding is written by the tiles of the image: they have to cover the batch's extent
     if ((H[i] + TH - 1) / TH * TH < Hp || (W[i] + QTILE_W - 1) / QTILE_W * QTILE_W < Wp) return 1;
+    for (int c = 0; c < 3; ++c) { na.mean[i][c] = mean[i * 3 + c]; na.std[i][c] = std[i * 3 + c]; }
+    na.mean[i][3] = 0.f; na.std[i][3] = 1.f;
   }
-  if (int rc = check_images(in_dev, outs.data(), C.data(), H, W, table_index, B, K, num_tables)) return rc;
+  if (int rc = check_images(in_dev, outs, C, H, W, table_index, B, K, num_tables)) return rc;
   if (int rc = prepare_device()) return rc;
   if (int rc = consume_device_status("dib_sparse_blur_normalized")) return rc;
-  BlurBatch tiled;
-  NormArgs na;
-  na.Hp = Hp; na.Wp = Wp; na.nhwc = channels_last ? 1 : 0;
-  tiled.n = 0;
-  int tiles = 0;
-  for (int i = 0; i < B; ++i) {
-    const ImageDesc d = quad_desc(in_dev[i], outs[i], 3, H[i], W[i], table_index[i], (const int *)tables_dev, K, tiles);
-    tiled.tile_begin[tiled.n] = tiles;
-    tiles += d.C * d.tiles_x * d.tiles_y;
-    for (int c = 0; c < 3; ++c) { na.mean[tiled.n][c] = mean[i * 3 + c]; na.std[tiled.n][c] = std[i * 3 + c]; }
-    na.mean[tiled.n][3] = 0.f; na.std[tiled.n][3] = 1.f;
-    tiled.img[tiled.n++] = d;
-  }
-  for (int k = tiled.n; k <= MAX_BATCH; ++k) tiled.tile_begin[k] = tiles;
-  tiled.total_tiles = tiles;
-  tiled.xcd_bands = 1;
-  const dim3 grid(quad_grid_x(tiled), tiled.n);
-  hipStream_t s = (hipStream_t)stream;
-  if (acc_mode == DIB_ACC_FAST16) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FAST16, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else if (acc_mode == DIB_ACC_FP32 && K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else if (acc_mode == DIB_ACC_FP32) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FP32, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else if (acc_mode == DIB_ACC_FMA16 && K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else if (acc_mode == DIB_ACC_FMA16) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_FMA16, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else if (K == 128) hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 128>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  else hipLaunchKernelGGL((blur_quad_f16_norm_kernel<DIB_ACC_BITEXACT, 256>), grid, dim3(256), QLDS_BYTES, s, tiled, na);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  BlurBatch tiled;      // every image is blurred (above): image i is entry i of the launch
+  build_batch(tiled, QTILE_W, 1, in_dev, outs, C, H, W, table_index, 0, B, (const int *)tables_dev, K);
+  return launch("dib_sparse_blur_normalized", norm_kernel(acc_mode, K), dim3(grid_x(tiled), tiled.n), NORM_LDS, (hipStream_t)stream, tiled, na);
 }
 
 // Test hook (not part of the drop-in boundary): runs the generic kernel on fp16 images so the

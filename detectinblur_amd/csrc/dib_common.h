@@ -85,6 +85,11 @@ void set_error(const char *fmt, ...);
 // The `normalize` argument of the compaction entry points doubles as their flag word (include/dib.h): DIB_COMPACT_LARGE_WINDOW and
 // DIB_COMPACT_VRUNS are flags, anything else that is non-zero means "divide the PSF by its sum first".  Every launch decodes it here.
 inline bool compact_wants_normalize(int normalize) { return (normalize & ~(DIB_COMPACT_LARGE_WINDOW | DIB_COMPACT_VRUNS)) != 0; }
+// ... into the compaction kernels' own flag word (COMPACT_* above)
+inline int compact_kernel_flags(int normalize) {
+  return (compact_wants_normalize(normalize) ? COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? COMPACT_LARGE_WINDOW : 0) |
+         ((normalize & DIB_COMPACT_VRUNS) ? COMPACT_VRUNS : 0);
+}
 // dib_compact.hip: the launch behind dib_psf_compact_list; any_order = hipExtAnyOrderLaunch (see dib_step.hip)
 int compact_launch(const void *const *ptrs, int dtype, int B, int K, int normalize, int *tables, hipStream_t s, bool any_order);
 // dib_blur.hip: compaction + blur as ONE launch (fp16 PSFs and images, K = 128, default tiles, at most MAX_BATCH of each).

@@ -258,10 +258,7 @@ int dib::compact_launch(const void *const *ptrs, int dtype, int B, int K, int no
       pp.p[i] = ptrs[b0 + i];
     }
     int *t = tables + (size_t)b0 * stride;
-    // `normalize` doubles as the flag word: bit 3 (DIB_COMPACT_LARGE_WINDOW) selects the large-window segmentation, anything
-    // else that is non-zero means "divide by the sum first"
-    const int flags = (dib::compact_wants_normalize(normalize) ? COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? COMPACT_LARGE_WINDOW : 0) |
-                      ((normalize & DIB_COMPACT_VRUNS) ? COMPACT_VRUNS : 0);
+    const int flags = dib::compact_kernel_flags(normalize);
     if (dtype == DIB_F16 && K == 128) hipExtLaunchKernelGGL((dib::psf_compact_kernel<__half, 128>), dim3(n), dim3(dib::CT), 0, s, nullptr, nullptr, lflags, pp, flags, t);
     else if (dtype == DIB_F16) hipExtLaunchKernelGGL((dib::psf_compact_kernel<__half, 256>), dim3(n), dim3(dib::CT), 0, s, nullptr, nullptr, lflags, pp, flags, t);
     else if (K == 128) hipExtLaunchKernelGGL((dib::psf_compact_kernel<float, 128>), dim3(n), dim3(dib::CT), 0, s, nullptr, nullptr, lflags, pp, flags, t);
@@ -269,9 +266,6 @@ int dib::compact_launch(const void *const *ptrs, int dtype, int B, int K, int no
   }
   DIB_HIP_CHECK(hipGetLastError());
   return DIB_OK;
-}
-static int launch_compact(const void *const *ptrs, int dtype, int B, int K, int normalize, int *tables, hipStream_t s) {
-  return dib::compact_launch(ptrs, dtype, B, K, normalize, tables, s, false);
 }
 
 static int check_compact_args(const void *p, void *tables_dev, int dtype, int B, int K) {
@@ -287,14 +281,14 @@ extern "C" int dib_psf_compact(const void *psf_dev, int dtype, int B, int K, int
   const size_t bytes = (size_t)K * K * (dtype == DIB_F16 ? 2 : 4);
   std::vector<const void *> ptrs((size_t)B);
   for (int i = 0; i < B; ++i) ptrs[i] = (const char *)psf_dev + (size_t)i * bytes;
-  return launch_compact(ptrs.data(), dtype, B, K, normalize, (int *)tables_dev, (hipStream_t)stream);
+  return dib::compact_launch(ptrs.data(), dtype, B, K, normalize, (int *)tables_dev, (hipStream_t)stream, false);
 }
 
 extern "C" int dib_psf_compact_list(const void *const *psf_ptrs, int dtype, int B, int K, int normalize, void *tables_dev,
                                     void *stream) {
   int rc = check_compact_args(psf_ptrs, tables_dev, dtype, B, K);
   if (rc != DIB_OK || B == 0) return rc;
-  return launch_compact(psf_ptrs, dtype, B, K, normalize, (int *)tables_dev, (hipStream_t)stream);
+  return dib::compact_launch(psf_ptrs, dtype, B, K, normalize, (int *)tables_dev, (hipStream_t)stream, false);
 }
 
 // Test hook (not part of the drop-in boundary): the 256-thread compaction of the blur step's single launch
@@ -310,7 +304,7 @@ extern "C" int dib_debug_compact_wg256(const void *const *psf_ptrs, int B, int n
   if (!psf_ptrs || !tables_dev || B < 1 || B > dib::MAX_BATCH) { dib::set_error("dib_debug_compact_wg256: bad arguments"); return DIB_EINVAL; }
   dib::PsfPtrs pp;
   for (int i = 0; i < B; ++i) pp.p[i] = psf_ptrs[i];
-  const int flags = (dib::compact_wants_normalize(normalize) ? dib::COMPACT_NORMALIZE : 0) | ((normalize & DIB_COMPACT_LARGE_WINDOW) ? dib::COMPACT_LARGE_WINDOW : 0);
+  const int flags = dib::compact_kernel_flags(normalize) & ~dib::COMPACT_VRUNS;      // this hook has never written the vertical-run groups
   hipLaunchKernelGGL(dib::psf_compact_wg256_kernel, dim3(B), dim3(256), 19712, (hipStream_t)stream, pp, flags, (int *)tables_dev);
   DIB_HIP_CHECK(hipGetLastError());
   return DIB_OK;

@@ -78,6 +78,25 @@ int state_of(int dev, hipStream_t s, StepState **out) {
   *out = &it->second;
   return DIB_OK;
 }
+
+// What dib_blur_step and dib_blur_step_ws (`who`: the error texts' prefix) check first.
+int check_step_args(const char *who, const void *const *psf_ptrs, int psf_dtype, int num_psfs, int K, int flags) {
+  if (num_psfs <= 0 || !psf_ptrs) { set_error("%s: no PSFs", who); return DIB_EINVAL; }
+  if (K != 128 && K != 256) { set_error("%s: K must be 128 or 256, got %d", who, K); return DIB_EINVAL; }
+  if (psf_dtype != DIB_F16 && psf_dtype != DIB_F32) { set_error("%s: unknown PSF dtype %d", who, psf_dtype); return DIB_EINVAL; }
+  if (flags & ~(DIB_STEP_PSFS_COMPLETE | DIB_STEP_LARGE_WINDOW)) { set_error("%s: unknown flags 0x%x", who, flags); return DIB_EINVAL; }
+  return DIB_OK;
+}
+// The step's flags and mode as the compaction's flag word (`normalize`) and the blur's `acc_mode`.
+void decode_step_flags(int flags, int &normalize, int &acc_mode) {
+  if (flags & DIB_STEP_LARGE_WINDOW) {     // compact for and blur with the large LDS window
+    normalize = (normalize ? 1 : 0) | DIB_COMPACT_LARGE_WINDOW;
+    acc_mode |= DIB_WINDOW_LARGE;
+  }
+  if (acc_mode == DIB_ACC_FAST16) normalize = (normalize ? 1 : 0) | DIB_COMPACT_VRUNS;    // that mode walks the tables' vertical-run groups (always two launches)
+}
+// One launch for the whole step where the shapes allow it (dib_blur.hip: blur_step_fused_launch decides the rest); else compaction + blur.
+bool single_launch_eligible(int K, int psf_dtype, int dtype, int flags) { return K == 128 && psf_dtype == DIB_F16 && dtype == DIB_F16 && !(flags & DIB_STEP_LARGE_WINDOW); }
 }  // namespace
 
 extern "C" size_t dib_blur_step_workspace_bytes(int K, int num_psfs) {
@@ -90,15 +109,8 @@ extern "C" int dib_blur_step(const void *const *psf_ptrs, int psf_dtype, int num
                              const void *const *in_dev, void *const *out_dev, const int *C, const int *H, const int *W,
                              const int *table_index, int B, int dtype, int acc_mode, void *tables_dev, int flags,
                              void *stream) {
-  if (num_psfs <= 0 || !psf_ptrs) { set_error("dib_blur_step: no PSFs"); return DIB_EINVAL; }
-  if (K != 128 && K != 256) { set_error("dib_blur_step: K must be 128 or 256, got %d", K); return DIB_EINVAL; }
-  if (psf_dtype != DIB_F16 && psf_dtype != DIB_F32) { set_error("dib_blur_step: unknown PSF dtype %d", psf_dtype); return DIB_EINVAL; }
-  if (flags & ~(DIB_STEP_PSFS_COMPLETE | DIB_STEP_LARGE_WINDOW)) { set_error("dib_blur_step: unknown flags 0x%x", flags); return DIB_EINVAL; }
-  if (flags & DIB_STEP_LARGE_WINDOW) {     // compact for and blur with the large LDS window
-    normalize = (normalize ? 1 : 0) | DIB_COMPACT_LARGE_WINDOW;
-    acc_mode |= DIB_WINDOW_LARGE;
-  }
-  if (acc_mode == DIB_ACC_FAST16) normalize = (normalize ? 1 : 0) | DIB_COMPACT_VRUNS;    // that mode walks the tables' vertical-run groups (always two launches)
+  if (int rc = check_step_args("dib_blur_step", psf_ptrs, psf_dtype, num_psfs, K, flags)) return rc;
+  decode_step_flags(flags, normalize, acc_mode);
   // what an earlier launch on this device left in the status word (a hand-off that timed out, a table of the wrong geometry):
   // reported here, once, without any synchronisation
   if (int rc = consume_device_status("dib_blur_step")) return rc;
@@ -149,8 +161,7 @@ extern "C" int dib_blur_step(const void *const *psf_ptrs, int psf_dtype, int num
     sl.generation = handoff_generation(dev);
     DIB_HIP_CHECK(hipMemsetAsync(sl.sync, 0, SYNC_BYTES, s));
   }
-  // One launch for the whole step where the shapes allow it (dib_blur.hip: blur_step_f16_kernel); else compaction + blur.
-  if (K == 128 && psf_dtype == DIB_F16 && dtype == DIB_F16 && !(flags & DIB_STEP_LARGE_WINDOW)) {
+  if (single_launch_eligible(K, psf_dtype, dtype, flags)) {
     const int rc = blur_step_fused_launch(psf_ptrs, num_psfs, normalize, in_dev, out_dev, C, H, W, table_index, B, acc_mode, sl.buf, sl.sync,
                                           (unsigned *)((char *)sl.sync + COUNTER_BYTES), sl.target + (unsigned)num_psfs, s);
     if (rc <= 0) {
@@ -196,28 +207,21 @@ extern "C" int dib_blur_step_ws(const void *const *psf_ptrs, int psf_dtype, int 
                                 const void *const *in_dev, void *const *out_dev, const int *C, const int *H, const int *W,
                                 const int *table_index, int B, int dtype, int acc_mode, void *workspace_dev, size_t workspace_bytes,
                                 unsigned long long *ws_state, int flags, void *stream) {
-  if (num_psfs <= 0 || !psf_ptrs) { set_error("dib_blur_step_ws: no PSFs"); return DIB_EINVAL; }
-  if (K != 128 && K != 256) { set_error("dib_blur_step_ws: K must be 128 or 256, got %d", K); return DIB_EINVAL; }
-  if (psf_dtype != DIB_F16 && psf_dtype != DIB_F32) { set_error("dib_blur_step_ws: unknown PSF dtype %d", psf_dtype); return DIB_EINVAL; }
-  if (flags & ~(DIB_STEP_PSFS_COMPLETE | DIB_STEP_LARGE_WINDOW)) { set_error("dib_blur_step_ws: unknown flags 0x%x", flags); return DIB_EINVAL; }
+  if (int rc = check_step_args("dib_blur_step_ws", psf_ptrs, psf_dtype, num_psfs, K, flags)) return rc;
   if (!workspace_dev || ((uintptr_t)workspace_dev & 255) || !ws_state || workspace_bytes < dib_blur_step_workspace_bytes(K, num_psfs)) {
     set_error("dib_blur_step_ws: the workspace must be 256-byte aligned device memory of at least dib_blur_step_workspace_bytes(K, num_psfs) = %zu bytes, with its host state word",
               dib_blur_step_workspace_bytes(K, num_psfs));
     return DIB_EINVAL;
   }
   if (int rc = consume_device_status("dib_blur_step_ws")) return rc;
-  if (flags & DIB_STEP_LARGE_WINDOW) {
-    normalize = (normalize ? 1 : 0) | DIB_COMPACT_LARGE_WINDOW;
-    acc_mode |= DIB_WINDOW_LARGE;
-  }
-  if (acc_mode == DIB_ACC_FAST16) normalize = (normalize ? 1 : 0) | DIB_COMPACT_VRUNS;
+  decode_step_flags(flags, normalize, acc_mode);
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   DIB_HIP_CHECK(hipStreamIsCapturing(s, &cap));
   // layout: the hand-off words first (a fixed size), the tables behind them
   constexpr size_t SYNC_ALIGNED = (SYNC_BYTES + 255) & ~(size_t)255;
   int *tables = (int *)((char *)workspace_dev + SYNC_ALIGNED);
-  if (cap == hipStreamCaptureStatusNone && K == 128 && psf_dtype == DIB_F16 && dtype == DIB_F16 && !(flags & DIB_STEP_LARGE_WINDOW)) {
+  if (cap == hipStreamCaptureStatusNone && single_launch_eligible(K, psf_dtype, dtype, flags)) {
     unsigned *sync = (unsigned *)workspace_dev;
     if (!(*ws_state >> 32)) {
       DIB_HIP_CHECK(hipMemsetAsync(sync, 0, SYNC_BYTES, s));
