@@ -61,6 +61,8 @@ __device__ __forceinline__ void report_and_exit(unsigned code, unsigned detail) 
 }
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef unsigned uvec2 __attribute__((ext_vector_type(2)));       // a pair of 32-bit words: one 8-byte LDS element
+typedef __attribute__((address_space(3))) uvec2 lds_u2;           // ... in LDS
 
 constexpr int TILE_W = 256;
 constexpr int PQ = WIN_PITCH;         // LDS row pitch in 8-byte words (96)
@@ -73,6 +75,13 @@ static_assert(WIN_PITCH * 8 == 768, "the asm below hard-codes the LDS row pitch"
 // 2 x 32-bit vector operand of an inline-asm "=v" output to the same register.
 typedef unsigned long long u2;
 
+// A 64-bit address every lane holds the same value of, told to the compiler: two v_readfirstlane, the result lives in a
+// scalar register pair (what an "s" asm operand, a scalar load's base and a buffer descriptor need).
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long a) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // ---- -DDIB_PORTABLE_TAPS: the tap loops and the step's wait as plain C++ ---------------------------------------------------------
 // The hand-written loops below name vector and scalar registers and lean on what hipcc 7.2 does around them; a compiler that
 // allocates differently turns tests/test_kernel_resources.py red.  `make portable` (csrc/Makefile) builds libdib_hip_portable.so
@@ -80,8 +89,7 @@ typedef unsigned long long u2;
 // (bit-identical results -- the GPU suite runs green on it: DIB_HIP_LIB=.../libdib_hip_portable.so python -m pytest tests -m gpu),
 // scheduled by the compiler, slower and outside the register budget.  A way to keep working, not a product path.
 #ifdef DIB_PORTABLE_TAPS
-typedef unsigned uvec2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uvec2 lds_b64(unsigned addr) { return *(const __attribute__((address_space(3))) uvec2 *)(size_t)addr; }
+__device__ __forceinline__ uvec2 lds_b64(unsigned addr) { return *(const lds_u2 *)(size_t)addr; }
 __device__ __forceinline__ unsigned lds_b32(unsigned addr) { return *(const __attribute__((address_space(3))) unsigned *)(size_t)addr; }
 __device__ __forceinline__ _Float16 half_of(unsigned bits) { return __builtin_bit_cast(_Float16, (unsigned short)(bits & 0xffffu)); }
 // one tap on one packed register: the reference's multiply, rounded, then its add, rounded -- or (FUSED) one fused multiply-add
@@ -91,6 +99,22 @@ __device__ __forceinline__ h2 tap_pk(h2 acc, unsigned p_bits, _Float16 w) {
   const h2 p = __builtin_bit_cast(h2, p_bits);
   if constexpr (FUSED) return h2{(_Float16)__builtin_fmaf16(w, p.x, acc.x), (_Float16)__builtin_fmaf16(w, p.y, acc.y)};
   else { const h2 t = h2{(_Float16)(w * p.x), (_Float16)(w * p.y)}; return h2{(_Float16)(acc.x + t.x), (_Float16)(acc.y + t.y)}; }
+}
+// tap_loop_r8 (ROWS = 8, 768 bytes per LDS row) and tap_loop_quad (4 rows, the window's pitch) restated: row i of a tap feeds
+// acc[2i] and -- not in a HALF tile -- acc[2i + 1]
+template <bool FUSED, bool HALF, int ROWS, unsigned PITCH>
+__device__ __forceinline__ void portable_taps(h2 (&acc)[2 * ROWS], unsigned long long ltaps, int t0, int n, unsigned lane_addr) {
+  const unsigned *lt = reinterpret_cast<const unsigned *>(ltaps);
+  for (int t = t0; t < t0 + n; ++t) {
+    const unsigned word = lt[t];
+    const _Float16 w = half_of(word >> 16);
+    const unsigned at = lane_addr + (word & 0xffffu);
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+      if constexpr (HALF) acc[2 * i] = tap_pk<FUSED>(acc[2 * i], lds_b32(at + PITCH * i), w);
+      else { const uvec2 e = lds_b64(at + PITCH * i); acc[2 * i] = tap_pk<FUSED>(acc[2 * i], e.x, w); acc[2 * i + 1] = tap_pk<FUSED>(acc[2 * i + 1], e.y, w); }
+    }
+  }
 }
 #endif
 
@@ -123,38 +147,26 @@ __device__ __forceinline__ h2 tap_pk(h2 acc, unsigned p_bits, _Float16 w) {
 // HALF variant: a tile whose valid columns all lie in its first 128 (the right-hand edge column of an
 // image whose width is not a multiple of 256: 1333 = 5 x 256 + 53) only has the packed registers
 // {P[j], P[j+64]}: 4-byte LDS reads, 8 multiplies + 8 adds per tap instead of 16 + 16.
-#define DIB_MUL(b) "v_pk_mul_f16 v" #b ", %18, v" #b " op_sel:[1,0] op_sel_hi:[1,1]\n\t"
-#define DIB_ADD(b, i) "v_pk_add_f16 %" #i ", %" #i ", v" #b "\n\t"
-#define DIB_FMA(b, i) "v_pk_fma_f16 %" #i ", %18, v" #b ", %" #i " op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-#define DIB_MADD_A                                                                                          \
-  DIB_MUL(64) DIB_MUL(65) DIB_MUL(66) DIB_MUL(67) DIB_MUL(68) DIB_MUL(69) DIB_MUL(70) DIB_MUL(71) \
-  DIB_MUL(72) DIB_MUL(73) DIB_MUL(74) DIB_MUL(75) DIB_MUL(76) DIB_MUL(77) DIB_MUL(78) DIB_MUL(79) \
-  DIB_ADD(64, 0) DIB_ADD(65, 1) DIB_ADD(66, 2) DIB_ADD(67, 3) DIB_ADD(68, 4) DIB_ADD(69, 5) DIB_ADD(70, 6) DIB_ADD(71, 7) \
-  DIB_ADD(72, 8) DIB_ADD(73, 9) DIB_ADD(74, 10) DIB_ADD(75, 11) DIB_ADD(76, 12) DIB_ADD(77, 13) DIB_ADD(78, 14) DIB_ADD(79, 15)
-#define DIB_MADD_B                                                                                          \
-  DIB_MUL(80) DIB_MUL(81) DIB_MUL(82) DIB_MUL(83) DIB_MUL(84) DIB_MUL(85) DIB_MUL(86) DIB_MUL(87) \
-  DIB_MUL(88) DIB_MUL(89) DIB_MUL(90) DIB_MUL(91) DIB_MUL(92) DIB_MUL(93) DIB_MUL(94) DIB_MUL(95) \
-  DIB_ADD(80, 0) DIB_ADD(81, 1) DIB_ADD(82, 2) DIB_ADD(83, 3) DIB_ADD(84, 4) DIB_ADD(85, 5) DIB_ADD(86, 6) DIB_ADD(87, 7) \
-  DIB_ADD(88, 8) DIB_ADD(89, 9) DIB_ADD(90, 10) DIB_ADD(91, 11) DIB_ADD(92, 12) DIB_ADD(93, 13) DIB_ADD(94, 14) DIB_ADD(95, 15)
+// Row k of the tap sits in v[B + k] (B = 64: buffer A, 80: buffer B); i: the accumulator's operand number.
+#define DIB_MUL(B, k) "v_pk_mul_f16 v[" #B "+" #k "], %18, v[" #B "+" #k "] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+#define DIB_ADD(B, k, i) "v_pk_add_f16 %" #i ", %" #i ", v[" #B "+" #k "]\n\t"
+#define DIB_FMA(B, k, i) "v_pk_fma_f16 %" #i ", %18, v[" #B "+" #k "], %" #i " op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+#define DIB_MADD(B)                                                                                                         \
+  DIB_MUL(B, 0) DIB_MUL(B, 1) DIB_MUL(B, 2) DIB_MUL(B, 3) DIB_MUL(B, 4) DIB_MUL(B, 5) DIB_MUL(B, 6) DIB_MUL(B, 7)           \
+  DIB_MUL(B, 8) DIB_MUL(B, 9) DIB_MUL(B, 10) DIB_MUL(B, 11) DIB_MUL(B, 12) DIB_MUL(B, 13) DIB_MUL(B, 14) DIB_MUL(B, 15)     \
+  DIB_ADD(B, 0, 0) DIB_ADD(B, 1, 1) DIB_ADD(B, 2, 2) DIB_ADD(B, 3, 3) DIB_ADD(B, 4, 4) DIB_ADD(B, 5, 5) DIB_ADD(B, 6, 6) DIB_ADD(B, 7, 7) \
+  DIB_ADD(B, 8, 8) DIB_ADD(B, 9, 9) DIB_ADD(B, 10, 10) DIB_ADD(B, 11, 11) DIB_ADD(B, 12, 12) DIB_ADD(B, 13, 13) DIB_ADD(B, 14, 14) DIB_ADD(B, 15, 15)
 // DIB_ACC_FMA16: the same loop with ONE packed fused multiply-add per register (one rounding per tap
 // instead of two): half the tap arithmetic, not the reference's arithmetic.
-#define DIB_FMADD_A                                                                                         \
-  DIB_FMA(64, 0) DIB_FMA(65, 1) DIB_FMA(66, 2) DIB_FMA(67, 3) DIB_FMA(68, 4) DIB_FMA(69, 5) DIB_FMA(70, 6) DIB_FMA(71, 7) \
-  DIB_FMA(72, 8) DIB_FMA(73, 9) DIB_FMA(74, 10) DIB_FMA(75, 11) DIB_FMA(76, 12) DIB_FMA(77, 13) DIB_FMA(78, 14) DIB_FMA(79, 15)
-#define DIB_FMADD_B                                                                                         \
-  DIB_FMA(80, 0) DIB_FMA(81, 1) DIB_FMA(82, 2) DIB_FMA(83, 3) DIB_FMA(84, 4) DIB_FMA(85, 5) DIB_FMA(86, 6) DIB_FMA(87, 7) \
-  DIB_FMA(88, 8) DIB_FMA(89, 9) DIB_FMA(90, 10) DIB_FMA(91, 11) DIB_FMA(92, 12) DIB_FMA(93, 13) DIB_FMA(94, 14) DIB_FMA(95, 15)
-// HALF: row i of the tap sits in v[base + i]; it feeds the even accumulators (acc[i][0] = operand 2i)
-#define DIB_MADDH_A                                                                                         \
-  DIB_MUL(64) DIB_MUL(65) DIB_MUL(66) DIB_MUL(67) DIB_MUL(68) DIB_MUL(69) DIB_MUL(70) DIB_MUL(71) \
-  DIB_ADD(64, 0) DIB_ADD(65, 2) DIB_ADD(66, 4) DIB_ADD(67, 6) DIB_ADD(68, 8) DIB_ADD(69, 10) DIB_ADD(70, 12) DIB_ADD(71, 14)
-#define DIB_MADDH_B                                                                                         \
-  DIB_MUL(80) DIB_MUL(81) DIB_MUL(82) DIB_MUL(83) DIB_MUL(84) DIB_MUL(85) DIB_MUL(86) DIB_MUL(87) \
-  DIB_ADD(80, 0) DIB_ADD(81, 2) DIB_ADD(82, 4) DIB_ADD(83, 6) DIB_ADD(84, 8) DIB_ADD(85, 10) DIB_ADD(86, 12) DIB_ADD(87, 14)
-#define DIB_FMADDH_A                                                                                        \
-  DIB_FMA(64, 0) DIB_FMA(65, 2) DIB_FMA(66, 4) DIB_FMA(67, 6) DIB_FMA(68, 8) DIB_FMA(69, 10) DIB_FMA(70, 12) DIB_FMA(71, 14)
-#define DIB_FMADDH_B                                                                                        \
-  DIB_FMA(80, 0) DIB_FMA(81, 2) DIB_FMA(82, 4) DIB_FMA(83, 6) DIB_FMA(84, 8) DIB_FMA(85, 10) DIB_FMA(86, 12) DIB_FMA(87, 14)
+#define DIB_FMADD(B)                                                                                                        \
+  DIB_FMA(B, 0, 0) DIB_FMA(B, 1, 1) DIB_FMA(B, 2, 2) DIB_FMA(B, 3, 3) DIB_FMA(B, 4, 4) DIB_FMA(B, 5, 5) DIB_FMA(B, 6, 6) DIB_FMA(B, 7, 7) \
+  DIB_FMA(B, 8, 8) DIB_FMA(B, 9, 9) DIB_FMA(B, 10, 10) DIB_FMA(B, 11, 11) DIB_FMA(B, 12, 12) DIB_FMA(B, 13, 13) DIB_FMA(B, 14, 14) DIB_FMA(B, 15, 15)
+// HALF: row i of the tap sits in v[B + i]; it feeds the even accumulators (acc[i][0] = operand 2i)
+#define DIB_MADDH(B)                                                                                                        \
+  DIB_MUL(B, 0) DIB_MUL(B, 1) DIB_MUL(B, 2) DIB_MUL(B, 3) DIB_MUL(B, 4) DIB_MUL(B, 5) DIB_MUL(B, 6) DIB_MUL(B, 7)           \
+  DIB_ADD(B, 0, 0) DIB_ADD(B, 1, 2) DIB_ADD(B, 2, 4) DIB_ADD(B, 3, 6) DIB_ADD(B, 4, 8) DIB_ADD(B, 5, 10) DIB_ADD(B, 6, 12) DIB_ADD(B, 7, 14)
+#define DIB_FMADDH(B)                                                                                                       \
+  DIB_FMA(B, 0, 0) DIB_FMA(B, 1, 2) DIB_FMA(B, 2, 4) DIB_FMA(B, 3, 6) DIB_FMA(B, 4, 8) DIB_FMA(B, 5, 10) DIB_FMA(B, 6, 12) DIB_FMA(B, 7, 14)
 #define DIB_READ8(base)                                                                                      \
   "v_mad_u32_u16 v96, %19, 1, %23\n\t"                                                                       \
   "ds_read_b64 v[" #base ":" #base "+1], v96\n\tds_read_b64 v[" #base "+2:" #base "+3], v96 offset:768\n\t"   \
@@ -176,20 +188,7 @@ __device__ __forceinline__ h2 tap_pk(h2 acc, unsigned p_bits, _Float16 w) {
 template <bool FUSED, bool HALF>
 __device__ __forceinline__ void tap_loop_r8(h2 (&acc)[8][2], unsigned long long ltaps, int t0, int n, unsigned lane_addr) {
 #ifdef DIB_PORTABLE_TAPS
-  {
-    const unsigned *lt = reinterpret_cast<const unsigned *>(ltaps);
-    for (int t = t0; t < t0 + n; ++t) {
-      const unsigned word = lt[t];
-      const _Float16 w = half_of(word >> 16);
-      const unsigned at = lane_addr + (word & 0xffffu);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if constexpr (HALF) acc[i][0] = tap_pk<FUSED>(acc[i][0], lds_b32(at + 768u * i), w);
-        else { const uvec2 e = lds_b64(at + 768u * i); acc[i][0] = tap_pk<FUSED>(acc[i][0], e.x, w); acc[i][1] = tap_pk<FUSED>(acc[i][1], e.y, w); }
-      }
-    }
-    return;
-  }
+  return portable_taps<FUSED, HALF, 8, 768u>(reinterpret_cast<h2 (&)[16]>(acc), ltaps, t0, n, lane_addr);
 #endif
   // cnt = taps left minus one: the borrow of its decrement ends the loop (n >= 1 in every segment)
   unsigned toff = (unsigned)__builtin_amdgcn_readfirstlane(t0 * 4), cnt = (unsigned)__builtin_amdgcn_readfirstlane(n - 1);
@@ -224,11 +223,11 @@ __device__ __forceinline__ void tap_loop_r8(h2 (&acc)[8][2], unsigned long long 
         "memory")
 #define DIB_W_DRAIN "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"
   if constexpr (HALF) {
-    if constexpr (FUSED) { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8H(64), DIB_READ8H(80), DIB_FMADDH_A, DIB_FMADDH_B); }
-    else { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8H(64), DIB_READ8H(80), DIB_MADDH_A, DIB_MADDH_B); }
+    if constexpr (FUSED) { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8H(64), DIB_READ8H(80), DIB_FMADDH(64), DIB_FMADDH(80)); }
+    else { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8H(64), DIB_READ8H(80), DIB_MADDH(64), DIB_MADDH(80)); }
   } else {
-    if constexpr (FUSED) { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8(64), DIB_READ8(80), DIB_FMADD_A, DIB_FMADD_B); }
-    else { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8(64), DIB_READ8(80), DIB_MADD_A, DIB_MADD_B); }
+    if constexpr (FUSED) { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8(64), DIB_READ8(80), DIB_FMADD(64), DIB_FMADD(80)); }
+    else { DIB_R8_ASM(DIB_W_DRAIN, DIB_READ8(64), DIB_READ8(80), DIB_MADD(64), DIB_MADD(80)); }
   }
 #undef DIB_W_DRAIN
 #undef DIB_R8_ASM
@@ -237,15 +236,11 @@ __device__ __forceinline__ void tap_loop_r8(h2 (&acc)[8][2], unsigned long long 
 }
 #undef DIB_MUL
 #undef DIB_ADD
-#undef DIB_MADD_A
-#undef DIB_MADD_B
 #undef DIB_FMA
-#undef DIB_FMADD_A
-#undef DIB_FMADD_B
-#undef DIB_MADDH_A
-#undef DIB_MADDH_B
-#undef DIB_FMADDH_A
-#undef DIB_FMADDH_B
+#undef DIB_MADD
+#undef DIB_FMADD
+#undef DIB_MADDH
+#undef DIB_FMADDH
 #undef DIB_READ8
 #undef DIB_READ8H
 #undef DIB_NEXTTAP
@@ -266,8 +261,7 @@ __device__ __forceinline__ void tap_loop_fp32(float (&acc)[R][4], const unsigned
     const unsigned a = lane_addr + (lt & 0xffffu);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-      typedef unsigned uvec2 __attribute__((ext_vector_type(2)));
-      const uvec2 q = *(const __attribute__((address_space(3))) uvec2 *)(size_t)(a + (unsigned)(i * PQ * 8));
+      const uvec2 q = *(const lds_u2 *)(size_t)(a + (unsigned)(i * PQ * 8));
       const float p0 = (float)__builtin_bit_cast(_Float16, (unsigned short)(q.x & 0xffffu));
       const float p1 = (float)__builtin_bit_cast(_Float16, (unsigned short)(q.x >> 16));
       const float p2 = (float)__builtin_bit_cast(_Float16, (unsigned short)(q.y & 0xffffu));
@@ -289,9 +283,8 @@ __device__ __forceinline__ void stamp(unsigned long long *dbg, int slot) {
 // a 32-bit per-lane byte offset (voffset) plus a scalar row offset (soffset) -- no 64-bit address
 // arithmetic on the vector ALU, which the arithmetic of the co-resident waves keeps busy.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *img_base, int ch, int H, int W) {
-  const unsigned long long a = (unsigned long long)img_base + (unsigned long long)ch * H * W * 2ull;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, H * W * 2, 0x00020000);
+  const unsigned long long a = uniform64((unsigned long long)img_base + (unsigned long long)ch * H * W * 2ull);
+  return __builtin_amdgcn_make_buffer_rsrc((void *)a, 0, H * W * 2, 0x00020000);
 }
 
 constexpr int NW = 4;                       // waves per workgroup
@@ -375,8 +368,6 @@ __device__ __forceinline__ void issue_window_loads(unsigned (&v)[G][5], unsigned
 // ---- fill, part 2: the loaded values -> LDS words {P[j], P[j+64], P[j+128], P[j+192]} ---------------------
 // word j from c0..c3, word j+64 from c1..c4 (only lanes below the segment's column extent have one).
 // wp: LDS byte address of this lane's word in this wave's first row.
-typedef unsigned uvec2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) uvec2_t lds_u2;
 template <bool MASKED, int G>
 __device__ __forceinline__ void write_window_rows(unsigned wp, unsigned (&v)[G][5], unsigned zmask, bool second) {
 #pragma unroll
@@ -391,10 +382,10 @@ __device__ __forceinline__ void write_window_rows(unsigned wp, unsigned (&v)[G][
         if (((zmask >> k) & 1u) || ((zmask >> (8 + g)) & 1u)) v[g][k] = 0;
     }
     const unsigned w0 = v[g][0] | (v[g][1] << 16), w1 = v[g][2] | (v[g][3] << 16);
-    *(lds_u2 *)(size_t)(wp + (unsigned)(g * PQ * 8)) = uvec2_t{w0, w1};
+    *(lds_u2 *)(size_t)(wp + (unsigned)(g * PQ * 8)) = uvec2{w0, w1};
     // {c1, c2} and {c3, c4}: funnel shifts of the words above (one VALU instruction each)
     if (second)
-      *(lds_u2 *)(size_t)(wp + (unsigned)((g * PQ + 64) * 8)) = uvec2_t{__builtin_amdgcn_alignbit(w1, w0, 16), __builtin_amdgcn_alignbit(v[g][4], w1, 16)};
+      *(lds_u2 *)(size_t)(wp + (unsigned)((g * PQ + 64) * 8)) = uvec2{__builtin_amdgcn_alignbit(w1, w0, 16), __builtin_amdgcn_alignbit(v[g][4], w1, 16)};
   }
 }
 template <int G>
@@ -412,9 +403,7 @@ __device__ __forceinline__ void write_window(unsigned wp, unsigned (&v)[G][5], u
 template <int ACC, int R>
 __device__ __forceinline__ void store_tile(const h2 (&acc)[R][2], const float (&acc32)[R][4], void *out_base, int ch, int H, int W, int x0,
                                            int y0, int lane, int wave) {
-  const unsigned long long pa = (unsigned long long)out_base + (unsigned long long)ch * H * W * 2ull;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pa), hi = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32));
-  void *plane = (void *)(((unsigned long long)hi << 32) | lo);
+  void *plane = (void *)uniform64((unsigned long long)out_base + (unsigned long long)ch * H * W * 2ull);
   const int w2 = W * 2;
   const int xr = W - x0 - lane;  // columns remaining for this lane
   const unsigned voff = 2u * (unsigned)(x0 + lane), oob = 0x7ffffff0u;
@@ -467,6 +456,7 @@ __device__ __forceinline__ void blur_tile_f16(const ImageDesc &d, const int *__r
   const int mode = pad_mode_for(K, H, W);
   const int nsegs = tab[HDR_NSEGS];
   const uint4 *segs = reinterpret_cast<const uint4 *>(tab + table_segs_off(K));
+  // uniform64(), written out: through the helper hipcc 7.2 schedules the prologue of the DIB_ACC_FP32 instantiation differently
   const unsigned long long la = (unsigned long long)(tab + table_ltaps_off(K));
   const unsigned long long ltaps = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(la >> 32)) << 32) |
                                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)la);
@@ -523,6 +513,27 @@ __device__ __forceinline__ bool band_entry(int T, int x, int t, int &local) {
   local = lo + t;
   return t < hi - lo;
 }
+// Tile index inside the image (channel-major order) -> channel, tile column and tile row.
+__device__ __forceinline__ void tile_of_local(const ImageDesc &d, int local, int &ch, int &tx, int &ty) {
+  const int per_ch = d.tiles_x * d.tiles_y;
+  ch = magic_div(local, d.inv_per_ch);
+  local -= ch * per_ch;
+  ty = magic_div(local, d.inv_tiles_x);
+  tx = local - ty * d.tiles_x;
+}
+// Entry `entry` of XCD list `list` of image d -> channel and tile; false past the end of the band.
+__device__ __forceinline__ bool tile_of_entry(const ImageDesc &d, int list, int entry, int &ch, int &tx, int &ty) {
+  int local;
+  if (!band_entry(d.C * d.tiles_x * d.tiles_y, list, entry, local)) return false;
+  tile_of_local(d, local, ch, tx, ty);
+  return true;
+}
+// Prologue = two scalar round trips.  First: the whole descriptor, K and the table base, requested together (left to
+// hipcc the fields are fetched one use at a time, a wait in front of each: six dependent round trips per workgroup).
+__device__ __forceinline__ void pin_desc(const ImageDesc &d) {
+  asm volatile("" ::"s"(d.in), "s"(d.out), "s"(d.C), "s"(d.H), "s"(d.W), "s"(d.table), "s"(d.tiles_x), "s"(d.tiles_y),
+               "s"(d.inv_per_ch), "s"(d.inv_tiles_x), "s"(d.tab));
+}
 
 // =============================================================================================
 // Default ("quad") shape: 128 x 32 tiles, 4 waves, eight workgroups per CU (the kernel is a closed system: a CU's slots
@@ -570,88 +581,72 @@ static_assert(QGeom<true>::PITCH == 768 && QGeom<true>::ROWS % NW == 0 && QGeom<
 //   tap 6k+4: load Q <- w[6k+8..9] | read Y at offset(R.hi) | multiply-add X by weight(R.lo)
 //   tap 6k+5:                        read X at offset(P.lo) | multiply-add Y by weight(R.hi)
 // Operands: %0-%7 accumulators, %8 byte offset of the next ltap pair, %9 taps left, %10 ltaps, %11 lane base.
-#define DIBQ_ADD(b, i) "v_pk_add_f16 %" #i ", %" #i ", v" #b "\n\t"
-#define DIBQ_MUL(b, W) "v_pk_mul_f16 v" #b ", " W ", v" #b " op_sel:[1,0] op_sel_hi:[1,1]\n\t"
-#define DIBQ_FMA(b, i, W) "v_pk_fma_f16 %" #i ", " W ", v" #b ", %" #i " op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-#define DIBQ_MADD_X(W) DIBQ_MUL(32, W) DIBQ_MUL(33, W) DIBQ_MUL(34, W) DIBQ_MUL(35, W) DIBQ_MUL(36, W) DIBQ_MUL(37, W) DIBQ_MUL(38, W) DIBQ_MUL(39, W) \
-  DIBQ_ADD(32, 0) DIBQ_ADD(33, 1) DIBQ_ADD(34, 2) DIBQ_ADD(35, 3) DIBQ_ADD(36, 4) DIBQ_ADD(37, 5) DIBQ_ADD(38, 6) DIBQ_ADD(39, 7)
-#define DIBQ_MADD_Y(W) DIBQ_MUL(40, W) DIBQ_MUL(41, W) DIBQ_MUL(42, W) DIBQ_MUL(43, W) DIBQ_MUL(44, W) DIBQ_MUL(45, W) DIBQ_MUL(46, W) DIBQ_MUL(47, W) \
-  DIBQ_ADD(40, 0) DIBQ_ADD(41, 1) DIBQ_ADD(42, 2) DIBQ_ADD(43, 3) DIBQ_ADD(44, 4) DIBQ_ADD(45, 5) DIBQ_ADD(46, 6) DIBQ_ADD(47, 7)
-#define DIBQ_FMADD_X(W) DIBQ_FMA(32, 0, W) DIBQ_FMA(33, 1, W) DIBQ_FMA(34, 2, W) DIBQ_FMA(35, 3, W) DIBQ_FMA(36, 4, W) DIBQ_FMA(37, 5, W) DIBQ_FMA(38, 6, W) DIBQ_FMA(39, 7, W)
-#define DIBQ_FMADD_Y(W) DIBQ_FMA(40, 0, W) DIBQ_FMA(41, 1, W) DIBQ_FMA(42, 2, W) DIBQ_FMA(43, 3, W) DIBQ_FMA(44, 4, W) DIBQ_FMA(45, 5, W) DIBQ_FMA(46, 6, W) DIBQ_FMA(47, 7, W)
-#define DIBQ_READ(base, OFF)                                                                                 \
-  "v_mad_u32_u16 v48, " OFF ", 1, %11\n\t"                                                                    \
-  "ds_read_b64 v[" #base ":" #base "+1], v48\n\tds_read_b64 v[" #base "+2:" #base "+3], v48 offset:448\n\t"    \
-  "ds_read_b64 v[" #base "+4:" #base "+5], v48 offset:896\n\tds_read_b64 v[" #base "+6:" #base "+7], v48 offset:1344\n\t"
+// Row i of the tap sits in v[B + 2i : B + 2i + 1] (B = 32: buffer X, 40: buffer Y); register B + k feeds accumulator k.
+#define DIBQ_ADD(B, k) "v_pk_add_f16 %" #k ", %" #k ", v[" #B "+" #k "]\n\t"
+#define DIBQ_MUL(B, k, W) "v_pk_mul_f16 v[" #B "+" #k "], " W ", v[" #B "+" #k "] op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+#define DIBQ_FMA(B, k, W) "v_pk_fma_f16 %" #k ", " W ", v[" #B "+" #k "], %" #k " op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+#define DIBQ_MADD(B, W) DIBQ_MUL(B, 0, W) DIBQ_MUL(B, 1, W) DIBQ_MUL(B, 2, W) DIBQ_MUL(B, 3, W) DIBQ_MUL(B, 4, W) DIBQ_MUL(B, 5, W) DIBQ_MUL(B, 6, W) DIBQ_MUL(B, 7, W) \
+  DIBQ_ADD(B, 0) DIBQ_ADD(B, 1) DIBQ_ADD(B, 2) DIBQ_ADD(B, 3) DIBQ_ADD(B, 4) DIBQ_ADD(B, 5) DIBQ_ADD(B, 6) DIBQ_ADD(B, 7)
+#define DIBQ_FMADD(B, W) DIBQ_FMA(B, 0, W) DIBQ_FMA(B, 1, W) DIBQ_FMA(B, 2, W) DIBQ_FMA(B, 3, W) DIBQ_FMA(B, 4, W) DIBQ_FMA(B, 5, W) DIBQ_FMA(B, 6, W) DIBQ_FMA(B, 7, W)
 // HALF variant: a tile with at most 64 valid columns (the right-hand edge of an image whose width is not a multiple of
 // 128: 1333 = 10 x 128 + 53) only needs the first word {P[k], P[k+32]} of every element: 4-byte reads, 4 + 4 instead of
 // 8 + 8 arithmetic instructions per tap, on the even registers / accumulators.
-#define DIBQ_READH(base, OFF)                                                                                \
-  "v_mad_u32_u16 v48, " OFF ", 1, %11\n\t"                                                                    \
-  "ds_read_b32 v[" #base "], v48\n\tds_read_b32 v[" #base "+2], v48 offset:448\n\t"                            \
-  "ds_read_b32 v[" #base "+4], v48 offset:896\n\tds_read_b32 v[" #base "+6], v48 offset:1344\n\t"
-#define DIBQ_READ_L(base, OFF)                                                                               \
-  "v_mad_u32_u16 v48, " OFF ", 1, %11\n\t"                                                                    \
-  "ds_read_b64 v[" #base ":" #base "+1], v48\n\tds_read_b64 v[" #base "+2:" #base "+3], v48 offset:768\n\t"    \
-  "ds_read_b64 v[" #base "+4:" #base "+5], v48 offset:1536\n\tds_read_b64 v[" #base "+6:" #base "+7], v48 offset:2304\n\t"
-#define DIBQ_READH_L(base, OFF)                                                                              \
-  "v_mad_u32_u16 v48, " OFF ", 1, %11\n\t"                                                                    \
-  "ds_read_b32 v[" #base "], v48\n\tds_read_b32 v[" #base "+2], v48 offset:768\n\t"                            \
-  "ds_read_b32 v[" #base "+4], v48 offset:1536\n\tds_read_b32 v[" #base "+6], v48 offset:2304\n\t"
-#define DIBQ_MADDH_X(W) DIBQ_MUL(32, W) DIBQ_MUL(34, W) DIBQ_MUL(36, W) DIBQ_MUL(38, W) DIBQ_ADD(32, 0) DIBQ_ADD(34, 2) DIBQ_ADD(36, 4) DIBQ_ADD(38, 6)
-#define DIBQ_MADDH_Y(W) DIBQ_MUL(40, W) DIBQ_MUL(42, W) DIBQ_MUL(44, W) DIBQ_MUL(46, W) DIBQ_ADD(40, 0) DIBQ_ADD(42, 2) DIBQ_ADD(44, 4) DIBQ_ADD(46, 6)
-#define DIBQ_FMADDH_X(W) DIBQ_FMA(32, 0, W) DIBQ_FMA(34, 2, W) DIBQ_FMA(36, 4, W) DIBQ_FMA(38, 6, W)
-#define DIBQ_FMADDH_Y(W) DIBQ_FMA(40, 0, W) DIBQ_FMA(42, 2, W) DIBQ_FMA(44, 4, W) DIBQ_FMA(46, 6, W)
-#define DIBQ_LOAD(PAIR) "s_load_dwordx2 " PAIR ", %10, %8\n\ts_add_u32 %8, %8, 8\n\t"
-#define DIBQ_NEXT(LABEL) "s_sub_u32 %9, %9, 1\n\ts_cbranch_scc1 " LABEL "\n\t"
+#define DIBQ_MADDH(B, W) DIBQ_MUL(B, 0, W) DIBQ_MUL(B, 2, W) DIBQ_MUL(B, 4, W) DIBQ_MUL(B, 6, W) DIBQ_ADD(B, 0) DIBQ_ADD(B, 2) DIBQ_ADD(B, 4) DIBQ_ADD(B, 6)
+#define DIBQ_FMADDH(B, W) DIBQ_FMA(B, 0, W) DIBQ_FMA(B, 2, W) DIBQ_FMA(B, 4, W) DIBQ_FMA(B, 6, W)
+// The four rows of the tap at LDS offset OFF (the low 16 bits of a scalar) into buffer `base`; ADDR: the lane-base operand,
+// P1..P3: the byte offsets of rows 1..3 -- DIBQ_PITCH in the standard window, DIBQ_PITCH_L in the large one.
+#define DIBQ_READ(base, OFF, ADDR, P1, P2, P3)                                                                \
+  "v_mad_u32_u16 v48, " OFF ", 1, " ADDR "\n\t"                                                               \
+  "ds_read_b64 v[" #base ":" #base "+1], v48\n\tds_read_b64 v[" #base "+2:" #base "+3], v48 offset:" P1 "\n\t"  \
+  "ds_read_b64 v[" #base "+4:" #base "+5], v48 offset:" P2 "\n\tds_read_b64 v[" #base "+6:" #base "+7], v48 offset:" P3 "\n\t"
+#define DIBQ_READH(base, OFF, ADDR, P1, P2, P3)                                                               \
+  "v_mad_u32_u16 v48, " OFF ", 1, " ADDR "\n\t"                                                               \
+  "ds_read_b32 v[" #base "], v48\n\tds_read_b32 v[" #base "+2], v48 offset:" P1 "\n\t"                         \
+  "ds_read_b32 v[" #base "+4], v48 offset:" P2 "\n\tds_read_b32 v[" #base "+6], v48 offset:" P3 "\n\t"
+#define DIBQ_PITCH "448", "896", "1344"
+#define DIBQ_PITCH_L "768", "1536", "2304"
+#define DIBQ_LOAD(PAIR, LT, TOFF) "s_load_dwordx2 " PAIR ", " LT ", " TOFF "\n\ts_add_u32 " TOFF ", " TOFF ", 8\n\t"
+#define DIBQ_NEXT(CNT, LABEL) "s_sub_u32 " CNT ", " CNT ", 1\n\ts_cbranch_scc1 " LABEL "\n\t"
+// The 6-way unrolled loop of the table above, shared by tap_loop_quad and tap_loop_quad_fp32.  What differs per loop comes in
+// as arguments: PFX the label prefix, TOFF / CNT / LT the operands "byte offset of the next ltap pair" / "taps left" / "ltaps",
+// ARITH(B, W) the arithmetic on buffer B with the weight in the high half of W, RD the read macro and, behind it, its ADDR and
+// row offsets.
+#define DIBQ_LOOP6(PFX, TOFF, CNT, LT, ARITH, RD, ...) \
+  DIBQ_LOAD("s[36:37]", LT, TOFF) DIBQ_LOAD("s[38:39]", LT, TOFF) "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t" RD(32, "s36", __VA_ARGS__) \
+  "L" PFX "_loop%=:\n\t" \
+  "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[40:41]", LT, TOFF) RD(40, "s37", __VA_ARGS__) ARITH(32, "s36") DIBQ_NEXT(CNT, "L" PFX "_done%=") \
+  "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s38", __VA_ARGS__) ARITH(40, "s37") DIBQ_NEXT(CNT, "L" PFX "_done%=") \
+  "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[36:37]", LT, TOFF) RD(40, "s39", __VA_ARGS__) ARITH(32, "s38") DIBQ_NEXT(CNT, "L" PFX "_done%=") \
+  "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s40", __VA_ARGS__) ARITH(40, "s39") DIBQ_NEXT(CNT, "L" PFX "_done%=") \
+  "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[38:39]", LT, TOFF) RD(40, "s41", __VA_ARGS__) ARITH(32, "s40") DIBQ_NEXT(CNT, "L" PFX "_done%=") \
+  "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s36", __VA_ARGS__) ARITH(40, "s41") \
+  "s_sub_u32 " CNT ", " CNT ", 1\n\ts_cbranch_scc0 L" PFX "_loop%=\n\t" \
+  "L" PFX "_done%=:\n\t" \
+  "s_waitcnt lgkmcnt(0)"
+#define DIBQ_CLOBBERS \
+  "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", \
+  "s36", "s37", "s38", "s39", "s40", "s41", "scc", "memory"
 template <bool FUSED, bool HALF, bool L = false>
 __device__ __forceinline__ void tap_loop_quad(h2 (&acc)[8], unsigned long long ltaps, int t0, int n, unsigned lane_addr) {
 #ifdef DIB_PORTABLE_TAPS
-  {
-    constexpr unsigned PITCH_B = L ? 768u : 448u;
-    const unsigned *lt = reinterpret_cast<const unsigned *>(ltaps);
-    for (int t = t0; t < t0 + n; ++t) {
-      const unsigned word = lt[t];
-      const _Float16 w = half_of(word >> 16);
-      const unsigned at = lane_addr + (word & 0xffffu);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (HALF) acc[2 * i] = tap_pk<FUSED>(acc[2 * i], lds_b32(at + PITCH_B * i), w);
-        else { const uvec2 e = lds_b64(at + PITCH_B * i); acc[2 * i] = tap_pk<FUSED>(acc[2 * i], e.x, w); acc[2 * i + 1] = tap_pk<FUSED>(acc[2 * i + 1], e.y, w); }
-      }
-    }
-    return;
-  }
+  return portable_taps<FUSED, HALF, 4, L ? 768u : 448u>(acc, ltaps, t0, n, lane_addr);
 #endif
   unsigned toff = (unsigned)__builtin_amdgcn_readfirstlane(t0 * 4), cnt = (unsigned)__builtin_amdgcn_readfirstlane(n - 1);
   unsigned a[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) a[i] = __builtin_bit_cast(unsigned, acc[i]);
-#define DIB_RQ_ASM(RD, ARITH_X, ARITH_Y) \
-  asm volatile( \
-      DIBQ_LOAD("s[36:37]") DIBQ_LOAD("s[38:39]") "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t" RD(32, "s36") \
-      "Ldibq_loop%=:\n\t" \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[40:41]") RD(40, "s37") ARITH_X("s36") DIBQ_NEXT("Ldibq_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s38") ARITH_Y("s37") DIBQ_NEXT("Ldibq_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[36:37]") RD(40, "s39") ARITH_X("s38") DIBQ_NEXT("Ldibq_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s40") ARITH_Y("s39") DIBQ_NEXT("Ldibq_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBQ_LOAD("s[38:39]") RD(40, "s41") ARITH_X("s40") DIBQ_NEXT("Ldibq_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s36") ARITH_Y("s41") \
-      "s_sub_u32 %9, %9, 1\n\ts_cbranch_scc0 Ldibq_loop%=\n\t" \
-      "Ldibq_done%=:\n\t" \
-      "s_waitcnt lgkmcnt(0)" \
+#define DIB_RQ_ASM(ARITH, RD, ...) \
+  asm volatile(DIBQ_LOOP6("dibq", "%8", "%9", "%10", ARITH, RD, "%11", __VA_ARGS__) \
       : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+s"(toff), "+s"(cnt) \
       : "s"(ltaps), "v"(lane_addr) \
-      : "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", \
-        "s36", "s37", "s38", "s39", "s40", "s41", "scc", "memory")
-  if constexpr (L && FUSED && HALF) { DIB_RQ_ASM(DIBQ_READH_L, DIBQ_FMADDH_X, DIBQ_FMADDH_Y); }
-  else if constexpr (L && FUSED) { DIB_RQ_ASM(DIBQ_READ_L, DIBQ_FMADD_X, DIBQ_FMADD_Y); }
-  else if constexpr (L && HALF) { DIB_RQ_ASM(DIBQ_READH_L, DIBQ_MADDH_X, DIBQ_MADDH_Y); }
-  else if constexpr (L) { DIB_RQ_ASM(DIBQ_READ_L, DIBQ_MADD_X, DIBQ_MADD_Y); }
-  else if constexpr (FUSED && HALF) { DIB_RQ_ASM(DIBQ_READH, DIBQ_FMADDH_X, DIBQ_FMADDH_Y); }
-  else if constexpr (FUSED) { DIB_RQ_ASM(DIBQ_READ, DIBQ_FMADD_X, DIBQ_FMADD_Y); }
-  else if constexpr (HALF) { DIB_RQ_ASM(DIBQ_READH, DIBQ_MADDH_X, DIBQ_MADDH_Y); }
-  else { DIB_RQ_ASM(DIBQ_READ, DIBQ_MADD_X, DIBQ_MADD_Y); }
+      : DIBQ_CLOBBERS)
+#define DIB_RQ_PICK(...) \
+  if constexpr (FUSED && HALF) { DIB_RQ_ASM(DIBQ_FMADDH, DIBQ_READH, __VA_ARGS__); } \
+  else if constexpr (FUSED) { DIB_RQ_ASM(DIBQ_FMADD, DIBQ_READ, __VA_ARGS__); } \
+  else if constexpr (HALF) { DIB_RQ_ASM(DIBQ_MADDH, DIBQ_READH, __VA_ARGS__); } \
+  else { DIB_RQ_ASM(DIBQ_MADD, DIBQ_READ, __VA_ARGS__); }
+  if constexpr (L) { DIB_RQ_PICK(DIBQ_PITCH_L) } else { DIB_RQ_PICK(DIBQ_PITCH) }
+#undef DIB_RQ_PICK
 #undef DIB_RQ_ASM
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = __builtin_bit_cast(h2, a[i]);
@@ -665,28 +660,11 @@ __device__ __forceinline__ void tap_loop_quad(h2 (&acc)[8], unsigned long long l
 // one-tap LDS look-ahead and 6-way unrolled scalar side as tap_loop_quad.  Sixteen fp32 accumulators per lane: acc[4 i + m] =
 // row i, column j + 32 m.  Operands: %0-%15 accumulators, %16 byte offset of the next ltap pair, %17 taps left, %18 ltaps,
 // %19 lane base.
-#define DIBF_MIX(b, i, hs, W) "v_fma_mix_f32 %" #i ", " W ", v" #b ", %" #i " op_sel:[1," #hs ",0] op_sel_hi:[1,1,0]\n\t"
-#define DIBF_ROWS_X(W) DIBF_MIX(32, 0, 0, W) DIBF_MIX(32, 1, 1, W) DIBF_MIX(33, 2, 0, W) DIBF_MIX(33, 3, 1, W) DIBF_MIX(34, 4, 0, W) DIBF_MIX(34, 5, 1, W) DIBF_MIX(35, 6, 0, W) DIBF_MIX(35, 7, 1, W) \
-  DIBF_MIX(36, 8, 0, W) DIBF_MIX(36, 9, 1, W) DIBF_MIX(37, 10, 0, W) DIBF_MIX(37, 11, 1, W) DIBF_MIX(38, 12, 0, W) DIBF_MIX(38, 13, 1, W) DIBF_MIX(39, 14, 0, W) DIBF_MIX(39, 15, 1, W)
-#define DIBF_ROWS_Y(W) DIBF_MIX(40, 0, 0, W) DIBF_MIX(40, 1, 1, W) DIBF_MIX(41, 2, 0, W) DIBF_MIX(41, 3, 1, W) DIBF_MIX(42, 4, 0, W) DIBF_MIX(42, 5, 1, W) DIBF_MIX(43, 6, 0, W) DIBF_MIX(43, 7, 1, W) \
-  DIBF_MIX(44, 8, 0, W) DIBF_MIX(44, 9, 1, W) DIBF_MIX(45, 10, 0, W) DIBF_MIX(45, 11, 1, W) DIBF_MIX(46, 12, 0, W) DIBF_MIX(46, 13, 1, W) DIBF_MIX(47, 14, 0, W) DIBF_MIX(47, 15, 1, W)
+#define DIBF_MIX(B, k, i, hs, W) "v_fma_mix_f32 %" #i ", " W ", v[" #B "+" #k "], %" #i " op_sel:[1," #hs ",0] op_sel_hi:[1,1,0]\n\t"
+#define DIBF_ROWS(B, W) DIBF_MIX(B, 0, 0, 0, W) DIBF_MIX(B, 0, 1, 1, W) DIBF_MIX(B, 1, 2, 0, W) DIBF_MIX(B, 1, 3, 1, W) DIBF_MIX(B, 2, 4, 0, W) DIBF_MIX(B, 2, 5, 1, W) DIBF_MIX(B, 3, 6, 0, W) DIBF_MIX(B, 3, 7, 1, W) \
+  DIBF_MIX(B, 4, 8, 0, W) DIBF_MIX(B, 4, 9, 1, W) DIBF_MIX(B, 5, 10, 0, W) DIBF_MIX(B, 5, 11, 1, W) DIBF_MIX(B, 6, 12, 0, W) DIBF_MIX(B, 6, 13, 1, W) DIBF_MIX(B, 7, 14, 0, W) DIBF_MIX(B, 7, 15, 1, W)
 // HALF (at most 64 valid columns): the first word {P[k], P[k+32]} of every element only
-#define DIBF_ROWSH_X(W) DIBF_MIX(32, 0, 0, W) DIBF_MIX(32, 1, 1, W) DIBF_MIX(34, 4, 0, W) DIBF_MIX(34, 5, 1, W) DIBF_MIX(36, 8, 0, W) DIBF_MIX(36, 9, 1, W) DIBF_MIX(38, 12, 0, W) DIBF_MIX(38, 13, 1, W)
-#define DIBF_ROWSH_Y(W) DIBF_MIX(40, 0, 0, W) DIBF_MIX(40, 1, 1, W) DIBF_MIX(42, 4, 0, W) DIBF_MIX(42, 5, 1, W) DIBF_MIX(44, 8, 0, W) DIBF_MIX(44, 9, 1, W) DIBF_MIX(46, 12, 0, W) DIBF_MIX(46, 13, 1, W)
-#define DIBF_READ(base, OFF, P1, P2, P3)                                                                      \
-  "v_mad_u32_u16 v48, " OFF ", 1, %19\n\t"                                                                    \
-  "ds_read_b64 v[" #base ":" #base "+1], v48\n\tds_read_b64 v[" #base "+2:" #base "+3], v48 offset:" P1 "\n\t"  \
-  "ds_read_b64 v[" #base "+4:" #base "+5], v48 offset:" P2 "\n\tds_read_b64 v[" #base "+6:" #base "+7], v48 offset:" P3 "\n\t"
-#define DIBF_READH(base, OFF, P1, P2, P3)                                                                     \
-  "v_mad_u32_u16 v48, " OFF ", 1, %19\n\t"                                                                    \
-  "ds_read_b32 v[" #base "], v48\n\tds_read_b32 v[" #base "+2], v48 offset:" P1 "\n\t"                         \
-  "ds_read_b32 v[" #base "+4], v48 offset:" P2 "\n\tds_read_b32 v[" #base "+6], v48 offset:" P3 "\n\t"
-#define DIBF_RD_S(base, OFF) DIBF_READ(base, OFF, "448", "896", "1344")
-#define DIBF_RD_L(base, OFF) DIBF_READ(base, OFF, "768", "1536", "2304")
-#define DIBF_RDH_S(base, OFF) DIBF_READH(base, OFF, "448", "896", "1344")
-#define DIBF_RDH_L(base, OFF) DIBF_READH(base, OFF, "768", "1536", "2304")
-#define DIBF_LOAD(PAIR) "s_load_dwordx2 " PAIR ", %18, %16\n\ts_add_u32 %16, %16, 8\n\t"
-#define DIBF_NEXT(LABEL) "s_sub_u32 %17, %17, 1\n\ts_cbranch_scc1 " LABEL "\n\t"
+#define DIBF_ROWSH(B, W) DIBF_MIX(B, 0, 0, 0, W) DIBF_MIX(B, 0, 1, 1, W) DIBF_MIX(B, 2, 4, 0, W) DIBF_MIX(B, 2, 5, 1, W) DIBF_MIX(B, 4, 8, 0, W) DIBF_MIX(B, 4, 9, 1, W) DIBF_MIX(B, 6, 12, 0, W) DIBF_MIX(B, 6, 13, 1, W)
 template <bool HALF, bool L>
 __device__ __forceinline__ void tap_loop_quad_fp32(float (&acc)[16], unsigned long long ltaps, int t0, int n, unsigned lane_addr) {
 #ifdef DIB_PORTABLE_TAPS
@@ -713,28 +691,16 @@ __device__ __forceinline__ void tap_loop_quad_fp32(float (&acc)[16], unsigned lo
   }
 #endif
   unsigned toff = (unsigned)__builtin_amdgcn_readfirstlane(t0 * 4), cnt = (unsigned)__builtin_amdgcn_readfirstlane(n - 1);
-#define DIB_RF_ASM(RD, ARITH_X, ARITH_Y) \
-  asm volatile( \
-      DIBF_LOAD("s[36:37]") DIBF_LOAD("s[38:39]") "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t" RD(32, "s36") \
-      "Ldibf_loop%=:\n\t" \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBF_LOAD("s[40:41]") RD(40, "s37") ARITH_X("s36") DIBF_NEXT("Ldibf_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s38") ARITH_Y("s37") DIBF_NEXT("Ldibf_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBF_LOAD("s[36:37]") RD(40, "s39") ARITH_X("s38") DIBF_NEXT("Ldibf_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s40") ARITH_Y("s39") DIBF_NEXT("Ldibf_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" DIBF_LOAD("s[38:39]") RD(40, "s41") ARITH_X("s40") DIBF_NEXT("Ldibf_done%=") \
-      "s_waitcnt lgkmcnt(0)\n\t" RD(32, "s36") ARITH_Y("s41") \
-      "s_sub_u32 %17, %17, 1\n\ts_cbranch_scc0 Ldibf_loop%=\n\t" \
-      "Ldibf_done%=:\n\t" \
-      "s_waitcnt lgkmcnt(0)" \
+#define DIB_RF_ASM(ARITH, RD, ...) \
+  asm volatile(DIBQ_LOOP6("dibf", "%16", "%17", "%18", ARITH, RD, "%19", __VA_ARGS__) \
       : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8]), \
         "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]), "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]), "+s"(toff), "+s"(cnt) \
       : "s"(ltaps), "v"(lane_addr) \
-      : "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", \
-        "s36", "s37", "s38", "s39", "s40", "s41", "scc", "memory")
-  if constexpr (L && HALF) { DIB_RF_ASM(DIBF_RDH_L, DIBF_ROWSH_X, DIBF_ROWSH_Y); }
-  else if constexpr (L) { DIB_RF_ASM(DIBF_RD_L, DIBF_ROWS_X, DIBF_ROWS_Y); }
-  else if constexpr (HALF) { DIB_RF_ASM(DIBF_RDH_S, DIBF_ROWSH_X, DIBF_ROWSH_Y); }
-  else { DIB_RF_ASM(DIBF_RD_S, DIBF_ROWS_X, DIBF_ROWS_Y); }
+      : DIBQ_CLOBBERS)
+  if constexpr (L && HALF) { DIB_RF_ASM(DIBF_ROWSH, DIBQ_READH, DIBQ_PITCH_L); }
+  else if constexpr (L) { DIB_RF_ASM(DIBF_ROWS, DIBQ_READ, DIBQ_PITCH_L); }
+  else if constexpr (HALF) { DIB_RF_ASM(DIBF_ROWSH, DIBQ_READH, DIBQ_PITCH); }
+  else { DIB_RF_ASM(DIBF_ROWS, DIBQ_READ, DIBQ_PITCH); }
 #undef DIB_RF_ASM
 }
 
@@ -913,9 +879,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
     }
   }
   static_assert(HDR_NSEGS == 7 && HDR_K == 5 && HDR_WORDS == 8, "header words 4..7 in the asm above");
-  const unsigned long long la = (unsigned long long)(tab + table_ltaps_q_off(K));
-  const unsigned long long ltaps = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(la >> 32)) << 32) |
-                                   (unsigned)__builtin_amdgcn_readfirstlane((unsigned)la);
+  const unsigned long long ltaps = uniform64((unsigned long long)(tab + table_ltaps_q_off(K)));
   // STEP: the tile's origin lives in ONE scalar register (ty << 16 | tx; tiles per channel < 2^16, dib_sparse_blur checks) and is
   // unpacked where it is needed -- not kept as x0 and y0 across the window fill, where the step kernel has no register left.
   const int x0c = tx * QTILE_W, y0c = ty * TH, pxy = ty << 16 | tx;
@@ -933,13 +897,17 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
   // hoisted to here they would stay live across the 44 outstanding window loads and spill (64 registers = 8 waves / SIMD).
   // (the lane index itself comes from v_mbcnt: no input register to keep either)
   auto fresh_lane = [&]() { int l; asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l)); return l; };
-  typedef unsigned lds_u2v __attribute__((ext_vector_type(2)));
-  typedef __attribute__((address_space(3))) lds_u2v lds_u2;
 
+  // DIB_TIMELINE (diagnostic build only): where WHEN holds, wave 0's wall clock into the 8 bytes at SLOT behind the window.  A macro,
+  // not a lambda: the diagnostic build must stay the shipped kernel plus the stamps, and hipcc lays a lambda's tests out differently.
 #ifdef DIB_TIMELINE
-  if (!L && !STEP && wave == 0 && fresh_lane() == 0)
-    *(__attribute__((address_space(3))) unsigned long long *)(size_t)(lds0 + QGeom<false>::BYTES + 32) = __builtin_amdgcn_s_memrealtime();
+#define DIB_TL_STAMP(WHEN, SLOT) \
+  if (!L && !STEP && WHEN && wave == 0 && fresh_lane() == 0) \
+    *(__attribute__((address_space(3))) unsigned long long *)(size_t)(lds0 + QGeom<false>::BYTES + SLOT) = __builtin_amdgcn_s_memrealtime()
+#else
+#define DIB_TL_STAMP(WHEN, SLOT)
 #endif
+  DIB_TL_STAMP(true, 32);
   for (int sg = 0; sg < (STEP ? (nsegs & 0xffffff) : nsegs); ++sg) {
     if (sg > 0) seg = segs[sg];
     const Window w = window_of(seg);
@@ -995,10 +963,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
 #pragma unroll
         for (int k = 0; k < NK; ++k) v[g][k] = __builtin_amdgcn_raw_buffer_load_b16(in_rsrc, coff[k], so, 0);
       }
-#ifdef DIB_TIMELINE
-      if (!L && !STEP && sg == 0 && part == 0 && wave == 0 && fresh_lane() == 0)
-        *(__attribute__((address_space(3))) unsigned long long *)(size_t)(lds0 + QGeom<false>::BYTES + 40) = __builtin_amdgcn_s_memrealtime();
-#endif
+      DIB_TL_STAMP(sg == 0 && part == 0, 40);
       if (part == 0 && sg > 0) __syncthreads();  // every wave is done reading the previous window
       // Elements 0 .. 31 + column extent are read by the taps; writing all 56 of a row costs the same (an LDS store is
       // priced per instruction), lanes 56-63 own no element.  The two 16-bit values of a word are merged by v_perm_b32
@@ -1013,12 +978,12 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
 #pragma unroll
           for (int k = 0; k < NK; ++k)
             u[k] = (masked && (((zmask >> k) & 1u) || ((zmask >> (8 + part * GP + g)) & 1u))) ? 0u : (unsigned)(unsigned short)v[g][k];
-          lds_u2v e;
+          uvec2 e;
           e.x = u[0] | (u[1] << 16);
           e.y = u[2] | (u[3] << 16);
           *(lds_u2 *)(size_t)(wp + (unsigned)(g * QPITCH)) = e;
           if (wl < 32) {
-            lds_u2v f;
+            uvec2 f;
             f.x = u[2] | (u[3] << 16);
             f.y = u[4] | (u[5] << 16);
             *(lds_u2 *)(size_t)(wp + (unsigned)(g * QPITCH + 512)) = f;
@@ -1029,7 +994,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
 #pragma unroll
           for (int g = 0; g < GP; ++g) {
             if (part * GP + g >= GQ) continue;
-            lds_u2v e;
+            uvec2 e;
             typedef short s2v __attribute__((ext_vector_type(2)));
             e.x = __builtin_bit_cast(unsigned, s2v{v[g][0], v[g][1]});
             e.y = __builtin_bit_cast(unsigned, s2v{v[g][2], v[g][3]});
@@ -1043,7 +1008,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
 #pragma unroll
             for (int k = 0; k < 4; ++k)
               u[k] = (((zmask >> k) & 1u) || ((zmask >> (8 + part * GP + g)) & 1u)) ? 0u : (unsigned)(unsigned short)v[g][k];
-            lds_u2v e;
+            uvec2 e;
             e.x = u[0] | (u[1] << 16);
             e.y = u[2] | (u[3] << 16);
             *(lds_u2 *)(size_t)(wp + (unsigned)(g * QPITCH)) = e;
@@ -1052,10 +1017,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
       }
     }
     __syncthreads();
-#ifdef DIB_TIMELINE
-    if (!L && !STEP && sg == 0 && wave == 0 && fresh_lane() == 0)
-      *(__attribute__((address_space(3))) unsigned long long *)(size_t)(lds0 + QGeom<false>::BYTES + 16) = __builtin_amdgcn_s_memrealtime();
-#endif
+    DIB_TL_STAMP(sg == 0, 16);
     if constexpr (STEP) { if (sg == 0 && (nsegs >> 30)) wait_tables(); }
     const int tl = fresh_lane();
     const unsigned lane_addr = lds0 + (unsigned)((wave * 8 + (tl >> 5) * 4) * QPITCH + (tl & 31) * 8);
@@ -1064,9 +1026,7 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
       else tap_loop_quad_fp32<false, L>(acc32, ltaps, w.t0, w.n, lane_addr);
     } else if constexpr (ACC == DIB_ACC_FAST16) {
       // the segment's vertical-run groups: records from index t0 on (dib_common.h: vgroups)
-      const unsigned long long va = (unsigned long long)(tab + table_vgroups_off(K));
-      const unsigned long long vg = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(va >> 32)) << 32) |
-                                    (unsigned)__builtin_amdgcn_readfirstlane((unsigned)va);
+      const unsigned long long vg = uniform64((unsigned long long)(tab + table_vgroups_off(K)));
       if (!use_vruns) {
         if (W - x0f() <= 64) tap_loop_quad<true, true, L>(acc, ltaps, w.t0, w.n, lane_addr);
         else tap_loop_quad<true, false, L>(acc, ltaps, w.t0, w.n, lane_addr);
@@ -1081,18 +1041,15 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = h2{(_Float16)acc32[2 * i], (_Float16)acc32[2 * i + 1]};
   }
-#ifdef DIB_TIMELINE
-  if (!L && !STEP && wave == 0 && fresh_lane() == 0)
-    *(__attribute__((address_space(3))) unsigned long long *)(size_t)(lds0 + QGeom<false>::BYTES + 24) = __builtin_amdgcn_s_memrealtime();
-#endif
+  DIB_TL_STAMP(true, 24);
+#undef DIB_TL_STAMP
   // ---- store: a store instruction writes 32 columns of row y (lanes 0-31) and of row y + 4 (lanes 32-63); lanes
   // outside the image get an out-of-range buffer offset and are dropped by the range check ----------------------------
   if constexpr (NORM) {
     const int Hp = na->Hp, Wp = na->Wp, nhwc = na->nhwc;
     const float m = na->mean[img][ch], sd = na->std[img][ch];
-    const unsigned long long a = (unsigned long long)d.out + (nhwc ? (unsigned long long)ch * 4ull : (unsigned long long)ch * Hp * Wp * 4ull);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, Hp * Wp * 4 * (nhwc ? 3 : 1) - (nhwc ? ch * 4 : 0), 0x00020000);
+    const unsigned long long a = uniform64((unsigned long long)d.out + (nhwc ? (unsigned long long)ch * 4ull : (unsigned long long)ch * Hp * Wp * 4ull));
+    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a, 0, Hp * Wp * 4 * (nhwc ? 3 : 1) - (nhwc ? ch * 4 : 0), 0x00020000);
     const int x0 = x0f(), y0 = y0f();
     const int sl = fresh_lane();
     const int yl = y0 + wave * 8 + (sl >> 5) * 4, xl = x0 + (sl & 31);
@@ -1127,9 +1084,8 @@ __device__ __forceinline__ void blur_quad_tile_f16(const ImageDesc &d, const int
       // block in the immediate offset, the high halves stored straight from the registers -- no vector instruction at all
       // (the general form below costs ~45 per wave).  Written out: there is no builtin for the d16_hi stores.
       typedef int i4v __attribute__((ext_vector_type(4)));
-      const unsigned long long pa2 = (unsigned long long)d.out + (unsigned long long)chs * H * W * 2ull;   // as plane_rsrc
-      const i4v rs = {__builtin_amdgcn_readfirstlane((int)(unsigned)pa2), __builtin_amdgcn_readfirstlane((int)(unsigned)(pa2 >> 32)) & 0xffff,
-                      H * W * 2, 0x00020000};
+      const unsigned long long pa2 = uniform64((unsigned long long)d.out + (unsigned long long)chs * H * W * 2ull);   // as plane_rsrc
+      const i4v rs = {(int)(unsigned)pa2, (int)(unsigned)(pa2 >> 32) & 0xffff, H * W * 2, 0x00020000};
       int so = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1211,17 +1167,10 @@ __global__ __launch_bounds__(256, 8) void blur_quad_f16_kernel(BlurBatch batch, 
     nlds[TL_WORD + 3] = img_i;
   }
 #endif
-  // Prologue = two scalar round trips.  First: the whole descriptor, K and the table base, requested together (left to
-  // hipcc the fields are fetched one use at a time, a wait in front of each: six dependent round trips per workgroup).
   const ImageDesc d = batch.img[img_i];
-  asm volatile("" ::"s"(d.in), "s"(d.out), "s"(d.C), "s"(d.H), "s"(d.W), "s"(d.table), "s"(d.tiles_x), "s"(d.tiles_y),
-               "s"(d.inv_per_ch), "s"(d.inv_tiles_x), "s"(d.tab));
-  const int per_ch = d.tiles_x * d.tiles_y;
-  int local;
-  if (!band_entry(d.C * per_ch, blockIdx.x & 7, entry, local)) return;
-  const int ch = magic_div(local, d.inv_per_ch);
-  local -= ch * per_ch;
-  const int ty = magic_div(local, d.inv_tiles_x), tx = local - ty * d.tiles_x;
+  pin_desc(d);
+  int ch, tx, ty;
+  if (!tile_of_entry(d, blockIdx.x & 7, entry, ch, tx, ty)) return;
   blur_quad_tile_f16<ACC>(d, d.tab, K, ch, tx, ty, lds_addr(nlds), __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));
 #ifdef DIB_TIMELINE
   if (threadIdx.x == 0) {
@@ -1462,9 +1411,8 @@ __global__ __launch_bounds__(256, 8) void blur_step_f16_kernel(BlurBatch batch, 
 #ifdef DIB_STEP_STAMPS
   if (bdbg) bdbg[1] = __builtin_amdgcn_s_memrealtime();
 #endif
-  const int ch = magic_div(local, d.inv_per_ch);
-  local -= ch * per_ch;
-  const int ty = magic_div(local, d.inv_tiles_x), tx = local - ty * d.tiles_x;
+  int ch, tx, ty;
+  tile_of_local(d, local, ch, tx, ty);
   blur_quad_tile_f16<ACC, false, true>(d, d.tab, K, ch, tx, ty, lds_addr(nlds), wave, early, nsegs0, seg0, StepWait{(unsigned)(size_t)(__attribute__((address_space(3))) char *)nlds + QLDS_BYTES});
 #ifdef DIB_STEP_STAMPS
   if (bdbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); bdbg[2] = __builtin_amdgcn_s_memrealtime(); }
@@ -1480,8 +1428,7 @@ __global__ __launch_bounds__(256, 8) void blur_quad_f16_norm_kernel(BlurBatch ba
   constexpr int K = KC;
   extern __shared__ unsigned nlds[];
   const ImageDesc d = batch.img[blockIdx.y];
-  asm volatile("" ::"s"(d.in), "s"(d.out), "s"(d.C), "s"(d.H), "s"(d.W), "s"(d.table), "s"(d.tiles_x), "s"(d.tiles_y),
-               "s"(d.inv_per_ch), "s"(d.inv_tiles_x), "s"(d.tab));
+  pin_desc(d);
   const int per_ch = d.tiles_x * d.tiles_y;
   int local;
   if (!band_entry(d.C * per_ch, blockIdx.x & 7, blockIdx.x >> 3, local)) return;
@@ -1507,14 +1454,9 @@ __global__ __launch_bounds__(256, 8) void blur_quad_f32acc_kernel(BlurBatch batc
   constexpr int K = KC;
   extern __shared__ unsigned nlds[];
   const ImageDesc d = batch.img[blockIdx.y];
-  asm volatile("" ::"s"(d.in), "s"(d.out), "s"(d.C), "s"(d.H), "s"(d.W), "s"(d.table), "s"(d.tiles_x), "s"(d.tiles_y),
-               "s"(d.inv_per_ch), "s"(d.inv_tiles_x), "s"(d.tab));
-  const int per_ch = d.tiles_x * d.tiles_y;
-  int local;
-  if (!band_entry(d.C * per_ch, blockIdx.x & 7, blockIdx.x >> 3, local)) return;
-  const int ch = magic_div(local, d.inv_per_ch);
-  local -= ch * per_ch;
-  const int ty = magic_div(local, d.inv_tiles_x), tx = local - ty * d.tiles_x;
+  pin_desc(d);
+  int ch, tx, ty;
+  if (!tile_of_entry(d, blockIdx.x & 7, blockIdx.x >> 3, ch, tx, ty)) return;
   blur_quad_tile_f16<DIB_ACC_FP32>(d, d.tab, K, ch, tx, ty, lds_addr(nlds), __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));
 }
 
@@ -1525,12 +1467,8 @@ __global__ __launch_bounds__(256, 4) void blur_quad_large_f16_kernel(BlurBatch b
   constexpr int K = KC;
   extern __shared__ unsigned nlds[];
   const ImageDesc d = batch.img[blockIdx.y];
-  const int per_ch = d.tiles_x * d.tiles_y;
-  int local;
-  if (!band_entry(d.C * per_ch, blockIdx.x & 7, blockIdx.x >> 3, local)) return;
-  const int ch = magic_div(local, d.inv_per_ch);
-  local -= ch * per_ch;
-  const int ty = magic_div(local, d.inv_tiles_x), tx = local - ty * d.tiles_x;
+  int ch, tx, ty;
+  if (!tile_of_entry(d, blockIdx.x & 7, blockIdx.x >> 3, ch, tx, ty)) return;
   blur_quad_tile_f16<ACC, true>(d, d.tab, K, ch, tx, ty, lds_addr(nlds), __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));
 }
 
@@ -1547,9 +1485,8 @@ __global__ __launch_bounds__(64 * NW, NW) void blur_tiled_f16_kernel(BlurBatch b
     local = blockIdx.x;              // flat order (the traffic experiment): tile index = block index
     if (local >= d.C * per_ch) return;
   }
-  const int ch = magic_div(local, d.inv_per_ch);
-  local -= ch * per_ch;
-  const int ty = magic_div(local, d.inv_tiles_x), tx = local - ty * d.tiles_x;
+  int ch, tx, ty;
+  tile_of_local(d, local, ch, tx, ty);
   blur_tile_f16<ACC>(d, tables + (size_t)d.table * table_words(K), K, ch, tx, ty, lds, dbg);
 }
 
