@@ -602,14 +602,9 @@ def rasterize_psfs(traj, fractions, canvas=256, center=True, out_n=None, want64=
     return p64, p16
 
 
-def normalize_pad(images, means, stds, Hp, Wp, channels_last=False, out_sizes=None):
-    """images: list of 3 x H x W CUDA tensors (float16 or float32, one dtype); means / stds: [B,3] rows (anything
-    numpy can read; rounded to float32 like torch.as_tensor(row, dtype=float32)).  Returns the fp32 batch
-    [B,3,Hp,Wp] (memory format channels_last on request) holding (x - mean) / std inside each image and 0 in the
-    padding: engine.py:107-110 + net_transforms.py:112-121 + :238-247 in one launch.  `out_sizes` ([(Ho, Wo)] per image): each
-    image is also resized to that size on the way (bilinear, align_corners=False, scale recomputed from the sizes:
-    net_transforms.py:151-175 as ATen computes it on the GPU); an image whose size is already (Ho, Wo) is not interpolated."""
-    import ctypes
+def _epilogue_arguments(images, means, stds, what):
+    """The checked argument lists of the epilogue entry points: (first image, tensors kept alive, pointers, heights, widths, float32
+    means, float32 stds)."""
     import numpy as np
     B = len(images)
     first = images[0]
@@ -619,11 +614,50 @@ def normalize_pad(images, means, stds, Hp, Wp, channels_last=False, out_sizes=No
     keep, ptrs, Hs, Ws = [], [], [], []
     for img in images:
         if img.dtype != first.dtype or not img.is_cuda or img.dim() != 3 or img.shape[0] != 3:
-            raise ValueError("normalize_pad needs 3 x H x W CUDA images of one dtype")
+            raise ValueError("%s needs 3 x H x W CUDA images of one dtype" % what)
         img = img if img.is_contiguous() else img.contiguous()
         keep.append(img); ptrs.append(img.data_ptr()); Hs.append(int(img.shape[1])); Ws.append(int(img.shape[2]))
     m = np.ascontiguousarray(np.asarray(means, dtype=np.float64).reshape(B, 3).astype(np.float32))
     sd = np.ascontiguousarray(np.asarray(stds, dtype=np.float64).reshape(B, 3).astype(np.float32))
+    return first, keep, ptrs, Hs, Ws, m, sd
+
+
+def _resize_crop(first, ptrs, Hs, Ws, out_sizes, m, sd, Hc, Wc, channels_last, flags):
+    import ctypes
+    fp = ctypes.POINTER(ctypes.c_float)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    out = torch.empty((len(ptrs), 3, Hc, Wc), dtype=torch.float32, device=first.device, memory_format=fmt)
+    _lib.check(_lib.lib().dib_normalize_resize_crop(_lib.ptr_array(ptrs), _DT[first.dtype], _lib.int_array(Hs), _lib.int_array(Ws),
+                                                    _lib.int_array([int(o[0]) for o in out_sizes]), _lib.int_array([int(o[1]) for o in out_sizes]),
+                                                    len(ptrs), m.ctypes.data_as(fp), sd.ctypes.data_as(fp), out.data_ptr(), Hc, Wc,
+                                                    int(bool(channels_last)), flags, _stream(first.device)))
+    return out
+
+
+def normalize_crop(images, means, stds, Hc, Wc, channels_last=False, out_sizes=None, quantize=False):
+    """The estimator's input batch in one launch (dib_normalize_resize_crop): images / means / stds / out_sizes as in normalize_pad;
+    returns the fp32 batch [B,3,Hc,Wc] holding the top-left Hc x Wc corner of every normalised, resized image
+    (net_transforms.py:226-236, `crop_images`); Hc <= Ho[i], Wc <= Wo[i].  `quantize` (float16 images): every source pixel first goes
+    through `(img * 255).type(torch.uint8).type(torch.half) / 255` (engine_blur_estimator.py:217)."""
+    first, keep, ptrs, Hs, Ws, m, sd = _epilogue_arguments(images, means, stds, "normalize_crop")
+    sizes = list(zip(Hs, Ws)) if out_sizes is None else out_sizes
+    return _resize_crop(first, ptrs, Hs, Ws, sizes, m, sd, Hc, Wc, channels_last, _lib.DIB_EPILOGUE_QUANTIZE if quantize else 0)
+
+
+def normalize_pad(images, means, stds, Hp, Wp, channels_last=False, out_sizes=None, quantize=False):
+    """images: list of 3 x H x W CUDA tensors (float16 or float32, one dtype); means / stds: [B,3] rows (anything
+    numpy can read; rounded to float32 like torch.as_tensor(row, dtype=float32)).  Returns the fp32 batch
+    [B,3,Hp,Wp] (memory format channels_last on request) holding (x - mean) / std inside each image and 0 in the
+    padding: engine.py:107-110 + net_transforms.py:112-121 + :238-247 in one launch.  `out_sizes` ([(Ho, Wo)] per image): each
+    image is also resized to that size on the way (bilinear, align_corners=False, scale recomputed from the sizes:
+    net_transforms.py:151-175 as ATen computes it on the GPU); an image whose size is already (Ho, Wo) is not interpolated.
+    `quantize` (float16 images): the 8-bit quantisation of normalize_crop first (dib_normalize_resize_crop with DIB_EPILOGUE_PAD)."""
+    import ctypes
+    B = len(images)
+    first, keep, ptrs, Hs, Ws, m, sd = _epilogue_arguments(images, means, stds, "normalize_pad")
+    if quantize:
+        return _resize_crop(first, ptrs, Hs, Ws, list(zip(Hs, Ws)) if out_sizes is None else out_sizes, m, sd, Hp, Wp, channels_last,
+                            _lib.DIB_EPILOGUE_QUANTIZE | _lib.DIB_EPILOGUE_PAD)
     fmt = torch.channels_last if channels_last else torch.contiguous_format
     out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=first.device, memory_format=fmt)
     fp = ctypes.POINTER(ctypes.c_float)

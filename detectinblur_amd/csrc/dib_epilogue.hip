@@ -83,7 +83,28 @@ template <bool FMA> __device__ __forceinline__ float lerp2(float l0h, float l1h,
   return l0h * (l0w * p00 + l1w * p01) + l1h * (l0w * p10 + l1w * p11);
 }
 
-template <typename T, bool NHWC, bool FMA>
+// The estimator's input (engine_blur_estimator.py, and engine.evaluate's ensemble router) is the same pass with two differences,
+// both template parameters of the one kernel below:
+//   CROP   the batch is the top-left Hp x Wp corner of every resized image (net_transforms.py:226-236, `crop_images`): the caller
+//          guarantees Hp <= Ho[i] and Wp <= Wo[i], so no pixel is padding and the bounds test and the zeros go away;
+//   QUANT  (fp16 input) every SOURCE pixel is first put through the reference's 8-bit quantisation
+//          `(img * 255).type(torch.uint8).type(torch.half) / 255` (engine_blur_estimator.py:217) as ATen evaluates it on Half:
+//          a = half(float(x) * 255.f); k = uint8(int64(a)) (truncation); q = half(float(k) / 255.f).  IEEE divide, no contraction.
+//          (ATen's device kernel multiplies by float(1) / 255.f instead; for the 256 values of k both round to the same Half:
+//          tests/test_estimator_driver.py.)  Domain: finite x >= 0 with half(x * 255) < 256; outside it the conversion to int64
+//          is the compiler's, as in ATen.
+template <typename T, bool QUANT> __device__ __forceinline__ float load_pixel(const T *p) {
+#pragma clang fp contract(off)
+  if constexpr (QUANT) {
+    const _Float16 a = (_Float16)((float)*p * 255.f);
+    const unsigned char k = (unsigned char)(long long)(float)a;
+    return (float)(_Float16)((float)k / 255.f);
+  } else {
+    return (float)*p;
+  }
+}
+
+template <typename T, bool NHWC, bool FMA, bool CROP, bool QUANT>
 __global__ __launch_bounds__(256) void normalize_resize_pad_kernel(ResizeBatch b, float *__restrict__ out, int Hp, int Wp) {
 #pragma clang fp contract(off)
   const int img = blockIdx.z;
@@ -91,13 +112,13 @@ __global__ __launch_bounds__(256) void normalize_resize_pad_kernel(ResizeBatch b
   if (x >= Wp) return;
   const int H = b.H[img], W = b.W[img], Ho = b.Ho[img], Wo = b.Wo[img];
   float v[3] = {0.f, 0.f, 0.f};
-  if (y < Ho && x < Wo) {
+  if (CROP || (y < Ho && x < Wo)) {
     const T *p = reinterpret_cast<const T *>(b.in[img]);
     const size_t plane = (size_t)H * W;
     if (Ho == H && Wo == W) {
       const T *q = p + (size_t)y * W + x;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = ((float)q[c * plane] - b.mean[img][c]) / b.std[img][c];
+      for (int c = 0; c < 3; ++c) v[c] = (load_pixel<T, QUANT>(q + c * plane) - b.mean[img][c]) / b.std[img][c];
     } else {
       const float h1r = src_index<FMA>(b.rh[img], y), w1r = src_index<FMA>(b.rw[img], x);
       const int h1 = (int)h1r, w1 = (int)w1r;
@@ -107,8 +128,8 @@ __global__ __launch_bounds__(256) void normalize_resize_pad_kernel(ResizeBatch b
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float m = b.mean[img][c], sd = b.std[img][c];
-        const float p00 = ((float)q0[c * plane] - m) / sd, p01 = ((float)q0[c * plane + w1p] - m) / sd;
-        const float p10 = ((float)q1[c * plane] - m) / sd, p11 = ((float)q1[c * plane + w1p] - m) / sd;
+        const float p00 = (load_pixel<T, QUANT>(q0 + c * plane) - m) / sd, p01 = (load_pixel<T, QUANT>(q0 + c * plane + w1p) - m) / sd;
+        const float p10 = (load_pixel<T, QUANT>(q1 + c * plane) - m) / sd, p11 = (load_pixel<T, QUANT>(q1 + c * plane + w1p) - m) / sd;
         v[c] = lerp2<FMA>(l0h, l1h, l0w, l1w, p00, p01, p10, p11);
       }
     }
@@ -163,18 +184,20 @@ extern "C" int dib_normalize_pad(const void *const *in_dev, int dtype, const int
 static int g_resize_fma = 1;
 extern "C" void dib_debug_set_resize_contraction(int on) { g_resize_fma = on ? 1 : 0; }
 
-extern "C" int dib_normalize_resize_pad(const void *const *in_dev, int dtype, const int *H, const int *W, const int *Ho, const int *Wo, int B,
-                                        const float *mean, const float *std, float *out_dev, int Hp, int Wp, int channels_last,
-                                        void *stream) {
-  if (B < 0 || (B > 0 && (!in_dev || !H || !W || !Ho || !Wo || !mean || !std || !out_dev))) { set_error("dib_normalize_resize_pad: null pointer or negative batch"); return DIB_EINVAL; }
-  if (dtype != DIB_F16 && dtype != DIB_F32) { set_error("dib_normalize_resize_pad: unknown dtype %d", dtype); return DIB_EINVAL; }
-  if (Hp <= 0 || Wp <= 0) { set_error("dib_normalize_resize_pad: empty batch shape"); return DIB_EINVAL; }
+// The one launcher of normalize_resize_pad_kernel.  `crop`: Hp x Wp is the top-left corner every resized image must cover (nothing
+// is padded); otherwise the zero-padded extent every resized image must fit into.  `quantize`: fp16 input only.
+static int launch_resize(const char *who, const void *const *in_dev, int dtype, const int *H, const int *W, const int *Ho, const int *Wo, int B,
+                         const float *mean, const float *std, float *out_dev, int Hp, int Wp, int channels_last, bool crop, bool quantize,
+                         void *stream) {
+  if (B < 0 || (B > 0 && (!in_dev || !H || !W || !Ho || !Wo || !mean || !std || !out_dev))) { set_error("%s: null pointer or negative batch", who); return DIB_EINVAL; }
+  if (dtype != DIB_F16 && dtype != DIB_F32) { set_error("%s: unknown dtype %d", who, dtype); return DIB_EINVAL; }
+  if (quantize && dtype != DIB_F16) { set_error("%s: DIB_EPILOGUE_QUANTIZE needs fp16 images", who); return DIB_EINVAL; }
+  if (Hp <= 0 || Wp <= 0) { set_error("%s: empty batch shape", who); return DIB_EINVAL; }
   for (int i = 0; i < B; ++i) {
-    if (!in_dev[i] || H[i] <= 0 || W[i] <= 0 || Ho[i] <= 0 || Wo[i] <= 0 || Ho[i] > Hp || Wo[i] > Wp) {
-      set_error("dib_normalize_resize_pad: image %d is null, empty or (resized) larger than the batch", i);
-      return DIB_EINVAL;
-    }
-    if ((uintptr_t)in_dev[i] & (dtype == DIB_F16 ? 1 : 3)) { set_error("dib_normalize_resize_pad: image %d is misaligned", i); return DIB_EINVAL; }
+    if (!in_dev[i] || H[i] <= 0 || W[i] <= 0 || Ho[i] <= 0 || Wo[i] <= 0) { set_error("%s: image %d is null or empty", who, i); return DIB_EINVAL; }
+    if (crop && (Hp > Ho[i] || Wp > Wo[i])) { set_error("%s: image %d is (resized) smaller than the crop", who, i); return DIB_EINVAL; }
+    if (!crop && (Ho[i] > Hp || Wo[i] > Wp)) { set_error("%s: image %d is (resized) larger than the batch", who, i); return DIB_EINVAL; }
+    if ((uintptr_t)in_dev[i] & (dtype == DIB_F16 ? 1 : 3)) { set_error("%s: image %d is misaligned", who, i); return DIB_EINVAL; }
   }
   hipStream_t s = (hipStream_t)stream;
   for (int b0 = 0; b0 < B; b0 += MAX_BATCH) {
@@ -190,16 +213,32 @@ extern "C" int dib_normalize_resize_pad(const void *const *in_dev, int dtype, co
     }
     float *out = out_dev + (size_t)b0 * 3 * Hp * Wp;
     const dim3 grid((Wp + 255) / 256, Hp, n), block(256);
-#define DIB_LAUNCH_RESIZE(T, CL, FM) hipLaunchKernelGGL((normalize_resize_pad_kernel<T, CL, FM>), grid, block, 0, s, rb, out, Hp, Wp)
-    if (dtype == DIB_F16) {
-      if (channels_last) { if (g_resize_fma) DIB_LAUNCH_RESIZE(_Float16, true, true); else DIB_LAUNCH_RESIZE(_Float16, true, false); }
-      else { if (g_resize_fma) DIB_LAUNCH_RESIZE(_Float16, false, true); else DIB_LAUNCH_RESIZE(_Float16, false, false); }
-    } else {
-      if (channels_last) { if (g_resize_fma) DIB_LAUNCH_RESIZE(float, true, true); else DIB_LAUNCH_RESIZE(float, true, false); }
-      else { if (g_resize_fma) DIB_LAUNCH_RESIZE(float, false, true); else DIB_LAUNCH_RESIZE(float, false, false); }
-    }
+#define DIB_LAUNCH_RESIZE(T, CL, FM, CR, Q) hipLaunchKernelGGL((normalize_resize_pad_kernel<T, CL, FM, CR, Q>), grid, block, 0, s, rb, out, Hp, Wp)
+#define DIB_PICK_FMA(T, CL, CR, Q) do { if (g_resize_fma) DIB_LAUNCH_RESIZE(T, CL, true, CR, Q); else DIB_LAUNCH_RESIZE(T, CL, false, CR, Q); } while (0)
+#define DIB_PICK_LAYOUT(T, CR, Q) do { if (channels_last) DIB_PICK_FMA(T, true, CR, Q); else DIB_PICK_FMA(T, false, CR, Q); } while (0)
+#define DIB_PICK_CROP(T, Q) do { if (crop) DIB_PICK_LAYOUT(T, true, Q); else DIB_PICK_LAYOUT(T, false, Q); } while (0)
+    if (dtype == DIB_F32) DIB_PICK_CROP(float, false);
+    else if (quantize) DIB_PICK_CROP(_Float16, true);
+    else DIB_PICK_CROP(_Float16, false);
+#undef DIB_PICK_CROP
+#undef DIB_PICK_LAYOUT
+#undef DIB_PICK_FMA
 #undef DIB_LAUNCH_RESIZE
   }
   DIB_HIP_CHECK(hipGetLastError());
   return DIB_OK;
+}
+
+extern "C" int dib_normalize_resize_pad(const void *const *in_dev, int dtype, const int *H, const int *W, const int *Ho, const int *Wo, int B,
+                                        const float *mean, const float *std, float *out_dev, int Hp, int Wp, int channels_last,
+                                        void *stream) {
+  return launch_resize("dib_normalize_resize_pad", in_dev, dtype, H, W, Ho, Wo, B, mean, std, out_dev, Hp, Wp, channels_last, false, false, stream);
+}
+
+extern "C" int dib_normalize_resize_crop(const void *const *in_dev, int dtype, const int *H, const int *W, const int *Ho, const int *Wo, int B,
+                                         const float *mean, const float *std, float *out_dev, int Hc, int Wc, int channels_last, int flags,
+                                         void *stream) {
+  if (flags & ~(DIB_EPILOGUE_QUANTIZE | DIB_EPILOGUE_PAD)) { set_error("dib_normalize_resize_crop: unknown flags 0x%x", flags); return DIB_EINVAL; }
+  return launch_resize("dib_normalize_resize_crop", in_dev, dtype, H, W, Ho, Wo, B, mean, std, out_dev, Hc, Wc, channels_last,
+                       !(flags & DIB_EPILOGUE_PAD), (flags & DIB_EPILOGUE_QUANTIZE) != 0, stream);
 }

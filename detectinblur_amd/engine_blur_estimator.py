@@ -59,7 +59,7 @@ def accuracy(output, target, topk=(1,)):
 
 # ---- blur with the optional 800-px round trip ----------------------------------------------------------
 
-def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False, acc_mode=_lib.DIB_ACC_BITEXACT):
+def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False, acc_mode=_lib.DIB_ACC_BITEXACT, tables=None):
     """reference :69-79 around its private `manual_blur` (:27-67).  With resize_images every blurred image is first brought to
     height 800 (bilinear, aspect kept; a portrait image is transposed first and stays transposed), blurred, CROPPED to its
     ORIGINAL height x width from the top-left corner -- the reference takes `image_height` / `image_width` before the resize and
@@ -67,9 +67,10 @@ def blur_image_list(images_GPU, blur_dicts, psfs_GPU, resize_images=False, acc_m
     resample unless the crop ran into the resized image's edge).  Pinned by tests/golden/detector_pins.json
     (`estimator/*/blur_resize_quant`): the blur is the same HIP launch, on the resized image.
     `acc_mode` (this repo, --blur_acc_mode): the blur's arithmetic, handed to that launch in both forms (what it means for the
-    batch's PSFs is decided there: blur_ops.resolve_acc_mode)."""
+    batch's PSFs is decided there: blur_ops.resolve_acc_mode).  `tables` (this repo): the tap tables `_stage` had compacted ahead,
+    for the launch at the images' own size."""
     if not resize_images:
-        return blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU, acc_mode=acc_mode)
+        return blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU, acc_mode=acc_mode, tables=tables)
     shapes, work = {}, list(images_GPU)
     for i, (img, bd) in enumerate(zip(images_GPU, blur_dicts)):
         if not bd["blurring"]:
@@ -104,7 +105,7 @@ def _post(images_GPU, add_noise, noise_level, add_block, quantize_image, jpeg_co
             from .transforms import add_jpeg_artifact_to_image
             img = add_jpeg_artifact_to_image(img, jpeg_compressor, np.random.uniform(20, 90)).to(img.device)
         if quantize_image:
-            img = (img * 255).type(torch.uint8).type(torch.half) / 255
+            img = GeneralizedRCNNTransform.quantize(img)
         images_GPU[i] = img
     return images_GPU
 
@@ -114,12 +115,27 @@ def _jpeg(device):
     return DiffJPEG(height=100, width=100, differentiable=False, quality=10).to(device)
 
 
-def _stage(images_CPU, blur_dicts, device, with_psfs):
-    images = [im.half().to(device, non_blocking=True) for im in images_CPU]
-    psfs = None
-    if with_psfs:
-        psfs = [torch.HalfTensor(bd["psf"]).to(device, non_blocking=True) for bd in blur_dicts]
-    return images, psfs
+def _stage(images_CPU, targets, blur_dicts, device, with_psfs, want_tables=False, blur_acc_mode="bitexact"):
+    """Images as Half, targets and (with_psfs) PSFs on `device`: the detector engine's staging (engine._to_device), so a deferred
+    AugMix plan in blur_dict["augmix"] is applied on the way (augmix.apply_plans_device on a GPU, apply_deferred_host on the CPU),
+    the PSFs travel as one pinned block on the side stream, and `want_tables` has their tap tables compacted there for
+    `blur_image_list(tables=)`.  Returns (images, targets, psfs, tables)."""
+    from .engine import _to_device
+    images, targets_dev, psfs, _, _, _, tables = _to_device(images_CPU, targets, blur_dicts, device, with_psfs, want_tables=want_tables,
+                                                            blur_acc_mode=blur_acc_mode)
+    return images, targets_dev, psfs, tables
+
+
+def _batch(batcher, images, targets, quantize_image):
+    """The batcher's tensor for the images `_post` left.  `quantize_image`: the 8-bit quantisation (reference :217) is handed to
+    the batcher's fused launch (`pending_quantize`, one call) when that launch will take the batch -- Half images on the GPU -- and
+    applied here, as the reference does, otherwise."""
+    if quantize_image:
+        if all(im.dtype == torch.float16 for im in images) and batcher._qualifies_for_fused(images):
+            batcher.pending_quantize = True
+        else:
+            images = [batcher.quantize(im) for im in images]
+    return batcher(images, targets)[0].tensors
 
 
 def _targets(blur_dicts, device, LEHE_blur_seg):
@@ -150,12 +166,12 @@ def train_one_epoch(model, optimizer, criterion, data_loader, device, print_freq
         lr_scheduler = utils.warmup_lr_scheduler(optimizer, min(1000, len(data_loader) - 1), 1.0 / 1000)
     it = 0
     for images_CPU, targets, blur_dicts in logger.log_every(data_loader, print_freq, "Epoch: [{}]".format(epoch)):
-        images, psfs = _stage(images_CPU, blur_dicts, device, blur_train)
-        targets_dev = [{k: v.to(device) for k, v in t.items()} for t in targets]
+        images, targets_dev, psfs, tables = _stage(images_CPU, targets, blur_dicts, device, blur_train,
+                                                   gpu_blur and blur_train and not resize_images, blur_acc_mode)
         if gpu_blur and blur_train:
-            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode)
-        images = _post(images, add_noise, noise_level, add_block, quantize_image, jpeg)
-        batch = batcher([im.float() for im in images], targets_dev)[0].tensors
+            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode, tables)
+        images = _post(images, add_noise, noise_level, add_block, False, jpeg)      # the quantisation: _batch
+        batch = _batch(batcher, images, targets_dev, quantize_image)
         target = _targets(blur_dicts, device, LEHE_blur_seg)
         loss_dict = {"loss": criterion(model(batch), target)}
         losses = sum(loss for loss in loss_dict.values())
@@ -207,13 +223,14 @@ def evaluate(model, data_loader, device, distributed_mode=False, blurring_images
     topk = (1, 2)
     for images_CPU, targets, blur_dicts in logger.log_every(data_loader, 100, "Test:"):
         model_time = time.time()
-        images, psfs = _stage(images_CPU, blur_dicts, device, blurring_images)
+        images, _, psfs, tables = _stage(images_CPU, [], blur_dicts, device, blurring_images,
+                                         gpu_blur and blurring_images and not resize_images, blur_acc_mode)
         if gpu_blur:
             if psfs is None:      # the reference reads `psfs_GPU`, which only `blurring_images` assigns (:352-358, :361)
                 raise UnboundLocalError("local variable 'psfs_GPU' referenced before assignment")
-            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode)
-        images = _post(images, add_noise, noise_level, add_block, quantize_image, jpeg)
-        outputs = model(batcher([im.float() for im in images])[0].tensors)
+            blur_image_list(images, blur_dicts, psfs, resize_images, acc_mode, tables)
+        images = _post(images, add_noise, noise_level, add_block, False, jpeg)      # the quantisation: _batch
+        outputs = model(_batch(batcher, images, None, quantize_image))
         model_time = time.time() - model_time
         evaluator_time = time.time()
         target = _targets(blur_dicts, device, LEHE_blur_seg)
@@ -241,7 +258,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, blurring_images
             continue
         valid_class_count += 1
         totalAcc += int(torch.logical_and(mergedTargets == classInd, mergedPreds == mergedTargets).sum()) / class_count
-    totalAcc = totalAcc / valid_class_count
+    # no image with a label in 0..3 (a short 16-way run): the reference divides by zero here; the mean of no classes is reported as nan
+    totalAcc = totalAcc / valid_class_count if valid_class_count else float("nan")
     print("Top 1 Mean Acc: {0:.2f}%".format(totalAcc * 100))
     torch.set_num_threads(n_threads)
     if send_back_preds_targets:

@@ -45,5 +45,18 @@ class ResNet18(nn.Module):
         return self.fc(F.adaptive_avg_pool2d(x, 1).flatten(1))
 
 
-def resnet18(num_classes=1000):
-    return ResNet18(num_classes)
+def resnet18(num_classes=1000, pretrained=False):
+    """`pretrained` (reference train_blur_estimator.py:212, torchvision.models.resnet18(pretrained=True)): the ImageNet weights, from
+    a locally cached file (faster_rcnn.find_pretrained); never downloaded."""
+    model = ResNet18(num_classes)
+    if pretrained:
+        import torch
+        from .faster_rcnn import PRETRAINED_FILES, find_pretrained
+        path = find_pretrained("resnet18")
+        if path is None:
+            raise RuntimeError("pretrained=True: none of %s is in $DIB_WEIGHTS_DIR / the torch hub cache / ./weights and it "
+                               "cannot be downloaded here (no network)" % (PRETRAINED_FILES["resnet18"],))
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        # torchvision's layout: layerN.M.downsample.{0,1} and the rest name for name
+        model.load_state_dict(sd)
+    return model

@@ -62,7 +62,8 @@ class FasterRCNN(GeneralizedRCNN):
 
 # what the reference downloads (models/faster_rcnn.py:295-298; torchvision.models.resnet.model_urls['resnet50'])
 PRETRAINED_FILES = {"fasterrcnn_resnet50_fpn_coco": ("fasterrcnn_resnet50_fpn_coco-258fb6c6.pth",),
-                    "resnet50": ("resnet50-19c8e357.pth", "resnet50-0676ba61.pth")}
+                    "resnet50": ("resnet50-19c8e357.pth", "resnet50-0676ba61.pth"),
+                    "resnet18": ("resnet18-5c106cde.pth", "resnet18-f37072fd.pth")}      # reference train_blur_estimator.py:212
 
 
 def find_pretrained(kind):

@@ -39,9 +39,9 @@ class GeneralizedRCNNTransform(nn.Module):
         self.crop_images = crop_images
         self.training = training
         self.normalize_images = normalize_images
-        # Fused epilogue (csrc/dib_epilogue.hip): float conversion + normalisation + zero-padded batch in one launch for
-        # CUDA batches that need no resize; bit-identical to the module-by-module path below, which stays the checker
-        # (tests/test_epilogue_gpu.py) and serves every other case.
+        # Fused epilogue (csrc/dib_epilogue.hip): float conversion + normalisation + resize + zero-padded (or, with crop_images,
+        # cropped) batch in one launch for CUDA batches; bit-identical to the module-by-module path below, which stays the checker
+        # (tests/test_epilogue_gpu.py, tests/test_estimator_input_gpu.py) and serves every other case.
         self.fused = True
 
     _stat_cache = {}
@@ -127,12 +127,19 @@ class GeneralizedRCNNTransform(nn.Module):
             scale = self.max_size / hi
         return scale
 
-    def _qualifies_for_fused(self, images):
-        if not (self.fused and self.normalize_images and not self.crop_images and images):
+    def _qualifies_for_fused(self, images, pending=False):
+        """Whether `_forward_fused` takes this batch.  `pending`: with a blur still to be applied (`pending_blur`), which the crop
+        mode does not serve: such a blur is materialised first."""
+        if not (self.fused and self.normalize_images and images) or (pending and self.crop_images):
             return False
         first = images[0]
         return (first.is_cuda and first.dtype in (torch.float16, torch.float32)
                 and not any(i.dim() != 3 or i.shape[0] != 3 or i.dtype != first.dtype or not i.is_cuda for i in images))
+
+    @staticmethod
+    def quantize(image):
+        """The reference's 8-bit quantisation of an estimator input (engine_blur_estimator.py:217)."""
+        return (image * 255).type(torch.uint8).type(torch.half) / 255
 
     @staticmethod
     def _materialize(images, pending):
@@ -141,20 +148,22 @@ class GeneralizedRCNNTransform(nn.Module):
         index, tables, acc_mode = pending
         return blur_ops.sparse_blur(list(images), list(index), tables, acc_mode)
 
-    def _forward_fused(self, images, targets, newMeans, newSTDs, pending=None):
-        """None when the batch does not qualify (not on the GPU, mixed dtypes, crop mode, images that are not 3 x H x W);
+    def _forward_fused(self, images, targets, newMeans, newSTDs, pending=None, quantize=False):
+        """None when the batch does not qualify (not on the GPU, mixed dtypes, images that are not 3 x H x W, a crop of no pixels);
         generator draws are consumed exactly as the unfused path would.  Images that need the resize of :151-175 (every
         native-size COCO image) are resized by the same launch (dib_normalize_resize_pad).
+        `crop_images` (the estimator's batcher, :226-236): the batch is the top-left corner of every resized image, its extent the
+        smallest resized height and width floored to multiples of 32, written by one launch as well (dib_normalize_resize_crop).
+        `quantize` (`pending_quantize`, Half images): the estimator's 8-bit quantisation of the source pixels, in that launch.
         `pending` = (table_index, tables, acc_mode): the images are still UNBLURRED (engine.py, opt-in `FUSE_BLUR_EPILOGUE`); when
         no image needs a resize the blur and this epilogue are ONE launch (blur_ops.sparse_blur_normalized: the blurred fp16
         batch never exists), otherwise the blur is launched here first and everything goes on as usual."""
-        if not (self.fused and self.normalize_images and not self.crop_images and images):
+        if not self._qualifies_for_fused(images, pending is not None):
             return None
         first = images[0]
-        if not (first.is_cuda and first.dtype in (torch.float16, torch.float32)):
+        if quantize and first.dtype != torch.float16:
             return None
-        if any(i.dim() != 3 or i.shape[0] != 3 or i.dtype != first.dtype or not i.is_cuda for i in images):
-            return None
+        rng = torch.get_rng_state() if self.crop_images and self.training else None
         sizes = [self._target_size() for _ in images]           # one generator draw per image when training, in image order
         from .. import blur_ops
         n = len(images)
@@ -169,18 +178,28 @@ class GeneralizedRCNNTransform(nn.Module):
             out_hw.append((h, w) if scale == 1.0 else (int(h * scale), int(w * scale)))
         if any(oh <= 0 or ow <= 0 for oh, ow in out_hw):
             return None                                         # degenerate sliver: let interpolate raise what it raises
-        Hp = int(math.ceil(max(h for h, _ in out_hw) / 32.0) * 32)
-        Wp = int(math.ceil(max(w for _, w in out_hw) / 32.0) * 32)
-        batch = None
-        if pending is not None:
-            if out_hw == hw and first.dtype == torch.float16:
-                batch = blur_ops.sparse_blur_normalized(images, pending[0], pending[1], means, stds, Hp, Wp,
-                                                        getattr(self, "channels_last", False), pending[2], order=pending[3] if len(pending) > 3 else None)
-                self.last_epilogue = "fused into the blur" if batch is not None else "own launch"
+        channels_last = getattr(self, "channels_last", False)
+        if self.crop_images:
+            Hc = int(math.floor(min(h for h, _ in out_hw) / 32.0) * 32)
+            Wc = int(math.floor(min(w for _, w in out_hw) / 32.0) * 32)
+            if Hc == 0 or Wc == 0:
+                if rng is not None:
+                    torch.set_rng_state(rng)                    # the module path draws its sizes itself
+                return None
+            batch = blur_ops.normalize_crop(images, means, stds, Hc, Wc, channels_last, out_sizes=out_hw, quantize=quantize)
+        else:
+            Hp = int(math.ceil(max(h for h, _ in out_hw) / 32.0) * 32)
+            Wp = int(math.ceil(max(w for _, w in out_hw) / 32.0) * 32)
+            batch = None
+            if pending is not None:
+                if out_hw == hw and first.dtype == torch.float16:
+                    batch = blur_ops.sparse_blur_normalized(images, pending[0], pending[1], means, stds, Hp, Wp,
+                                                            channels_last, pending[2], order=pending[3] if len(pending) > 3 else None)
+                    self.last_epilogue = "fused into the blur" if batch is not None else "own launch"
+                if batch is None:
+                    images = self._materialize(images, pending[:3])
             if batch is None:
-                images = self._materialize(images, pending[:3])
-        if batch is None:
-            batch = blur_ops.normalize_pad(images, means, stds, Hp, Wp, getattr(self, "channels_last", False), out_sizes=out_hw)
+                batch = blur_ops.normalize_pad(images, means, stds, Hp, Wp, channels_last, out_sizes=out_hw, quantize=quantize)
         if targets is not None:
             for t, src, dst, scale in zip(targets, hw, out_hw, scales):
                 self._resize_target(t, src, dst, scale)
@@ -194,12 +213,15 @@ class GeneralizedRCNNTransform(nn.Module):
             if image.dim() != 3:
                 raise ValueError("images is expected to be a list of 3d tensors of shape [C, H, W], got {}".format(image.shape))
         pending = self.__dict__.pop("pending_blur", None)      # set by engine.py for ONE call: the images are still unblurred
-        if pending is not None and not self._qualifies_for_fused(images):
+        quantize = self.__dict__.pop("pending_quantize", False)    # set by engine_blur_estimator.py for ONE call: Half images, not yet quantised
+        if pending is not None and not self._qualifies_for_fused(images, True):
             images = self._materialize(images, pending[:3])
             pending = None
-        fused = self._forward_fused(images, targets, newMeans, newSTDs, pending)
+        fused = self._forward_fused(images, targets, newMeans, newSTDs, pending, quantize)
         if fused is not None:
             return fused
+        if quantize:
+            images = [self.quantize(i) for i in images]
         # Half images only arrive from engine.py when the fused path was expected to take them: convert as the
         # reference's engine would have (engine.py:107-110)
         images = [i.float() if i.dtype == torch.float16 else i for i in images]

@@ -208,6 +208,25 @@ int dib_normalize_resize_pad(const void *const *in_dev, int dtype, const int *H,
                              const float *mean, const float *std, float *out_dev, int Hp, int Wp, int channels_last,
                              void *stream);
 
+/* The estimator's input batch (engine_blur_estimator.py:221-258 and the ensemble router, engine.py:259-265, :354-366): the
+ * arguments and the arithmetic of dib_normalize_resize_pad, then the TOP-LEFT CROP of models/net_transforms.py:226-236
+ * (`crop_images`): out_dev is [B][3][Hc][Wc] fp32 (planar or channels-last as above) and holds rows 0..Hc-1, columns 0..Wc-1 of
+ * every resized, normalised image.  Hc <= Ho[i] and Wc <= Wo[i] for every image, or DIB_EINVAL: nothing is ever padded.  B > 32
+ * is split into launches of 32 images.  flags:
+ *   DIB_EPILOGUE_QUANTIZE  (fp16 images only, else DIB_EINVAL) every source pixel first goes through the reference's
+ *       `(img * 255).type(torch.uint8).type(torch.half) / 255` (engine_blur_estimator.py:217) as ATen evaluates it on Half:
+ *       a = half(float(x) * 255.f), k = a truncated to an integer (uint8(int64(a))), q = half(float(k) / 255.f); IEEE divide, no
+ *       contraction.  Domain: finite x >= 0 with half(x * 255) < 256 (every x <= 1.0029297); outside it the result is whatever the
+ *       compiler's Half -> int64 -> uint8 conversion gives, as in ATen.
+ *   DIB_EPILOGUE_PAD  the zero-padded batch of dib_normalize_resize_pad instead of the crop (Hc >= Ho[i], Wc >= Wo[i], pixels
+ *       outside an image become 0): dib_normalize_resize_pad with flags, for DIB_EPILOGUE_QUANTIZE in the detector's batch mode.
+ * Bit-identical to the unfused GPU path (quantise expression, .float(), normalize, interpolate, crop copy). */
+#define DIB_EPILOGUE_QUANTIZE 1
+#define DIB_EPILOGUE_PAD 2
+int dib_normalize_resize_crop(const void *const *in_dev, int dtype, const int *H, const int *W, const int *Ho, const int *Wo, int B,
+                              const float *mean, const float *std, float *out_dev, int Hc, int Wc, int channels_last, int flags,
+                              void *stream);
+
 /* The blur WITH that epilogue as its store phase: dib_sparse_blur + dib_normalize_pad in one launch, for batches whose images
  * need no resize (the model's internal scale factor is 1: BASELINE's synthetic 800 x 1333; the reference blurs, engine.py:101,
  * converts to float, :107-110, and normalises + pads inside the model, net_transforms.py:112-121, :238-247 -- the blurred fp16
