@@ -81,6 +81,10 @@ __device__ inline int map_coord(int s, int n, int pa, int pb, int mode, bool &ze
   return min(max(s, 0), n - 1);
 }
 
+// ReLU forward as torch computes it (clamp_min(0)): a NaN goes through; everything else that is not > 0 becomes +0.  Every fused ReLU of
+// the trunk uses this one form: a bare fmaxf(v, 0) returns 0 for a NaN and would hide a diverged activation from the loss.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 void set_error(const char *fmt, ...);
 // The `normalize` argument of the compaction entry points doubles as their flag word (include/dib.h): DIB_COMPACT_LARGE_WINDOW and
 // DIB_COMPACT_VRUNS are flags, anything else that is non-zero means "divide the PSF by its sum first".  Every launch decodes it here.

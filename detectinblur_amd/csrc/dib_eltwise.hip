@@ -12,7 +12,7 @@ __global__ __launch_bounds__(256) void bias_act_scalar_kernel(float *__restrict_
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float v = x[i] + bias[(int)(i % C)];
     if (RES) v += res[i];
-    if (RELU) v = fmaxf(v, 0.f);
+    if (RELU) v = relu_keep_nan(v);
     x[i] = v;
   }
 }
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void bias_act_transpose_kernel(const float *__
     const int r = r0 + ty + 4 * k;
     if (r < rows && c < cols) {
       float v = in[img + (size_t)r * cols + c] + (bias_on_cols ? bc : bias[r]);
-      if (RELU) v = fmaxf(v, 0.f);                               // as bias_act_kernel
+      if (RELU) v = relu_keep_nan(v);                            // as bias_act_kernel
       tile[ty + 4 * k][tx] = v;
     }
   }

@@ -20,7 +20,7 @@ struct F32Lane {
   typedef float4 Quad;
   static __device__ __forceinline__ void unpack(const Raw u, float v[N]) { v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; }
   static __device__ __forceinline__ Raw pack(const float v[N]) { return make_float4(v[0], v[1], v[2], v[3]); }
-  static __device__ __forceinline__ float relu(float v) { return fmaxf(v, 0.f); }
+  static __device__ __forceinline__ float relu(float v) { return relu_keep_nan(v); }
   // bit k = element k > 0
   static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
     return (u.x > 0.f ? 1 : 0) | (u.y > 0.f ? 2 : 0) | (u.z > 0.f ? 4 : 0) | (u.w > 0.f ? 8 : 0);
@@ -56,8 +56,7 @@ struct Bf16Lane {
   static __device__ __forceinline__ Raw pack(const float v[N]) {
     return make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
   }
-  // torch's relu (clamp_min): a NaN goes through
-  static __device__ __forceinline__ float relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
+  static __device__ __forceinline__ float relu(float v) { return relu_keep_nan(v); }
   // bit k = STORED element k > 0 (the value AFTER rounding: a positive fp32 below half of bf16's smallest denormal is stored
   // as zero and gets no gradient, as in the plain graph on the stored tensor)
   static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
@@ -198,11 +197,12 @@ __global__ __launch_bounds__(256) void topdown_merge_kernel(typename L::Raw *__r
 
 // ResNet stem: bias + ReLU + 3x3 / stride 2 / padding 1 max-pool of the first convolution's output in ONE pass.
 // relu and max commute, so pooled = relu(max over the window of (x + bias)); the backward pass needs, per pooled element, only
-// WHICH window position won (4 bits; 15 = the maximum was not positive, no gradient): the 550 MB activation is neither written
-// back nor re-read, and ATen's int64 index tensor (2 x the pooled output) disappears.  Window scan order and the strict `>`
-// are ATen's (max_pool2d: first maximum in row-major window order).  The 7x7 convolution in front has 3 input channels and stays
-// fp32 in both forms (models/backbone.py): x is fp32, the pooled maximum is stored as L's type, rounded once.  Rounding is
-// monotonic, so the recorded winner is also a maximum of the rounded values.  4 channels per lane.
+// WHICH window position won (4 bits; 15 = the maximum was neither positive nor NaN, no gradient): the 550 MB activation is
+// neither written back nor re-read, and ATen's int64 index tensor (2 x the pooled output) disappears.  Window scan order and the
+// selection `v > m || isnan(v)` are ATen's (max_pool2d: first maximum in row-major window order; a NaN beats everything, the
+// LAST NaN of a window is the recorded one), and a NaN maximum stays NaN as it does through torch's relu.  The 7x7 convolution in
+// front has 3 input channels and stays fp32 in both forms (models/backbone.py): x is fp32, the pooled maximum is stored as L's
+// type, rounded once.  Rounding is monotonic, so the recorded winner is also a maximum of the rounded values.  4 channels per lane.
 template <class L>
 __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float4 *__restrict__ x, const float4 *__restrict__ bias,
                                                            typename L::Quad *__restrict__ out, unsigned short *__restrict__ arg, int H,
@@ -230,15 +230,16 @@ __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const float4 *__rest
     const int h = oh * 2 - 1 + k / 3, w = ow * 2 - 1 + k % 3;
     const bool in = h >= 0 && h < H && w >= 0 && w < W;
     const float vx = in ? v[k].x + b.x : ninf, vy = in ? v[k].y + b.y : ninf, vz = in ? v[k].z + b.z : ninf, vw = in ? v[k].w + b.w : ninf;
-    if (vx > m.x) { m.x = vx; ax = k; }
-    if (vy > m.y) { m.y = vy; ay = k; }
-    if (vz > m.z) { m.z = vz; az = k; }
-    if (vw > m.w) { m.w = vw; aw = k; }
+    if (vx > m.x || vx != vx) { m.x = vx; ax = k; }
+    if (vy > m.y || vy != vy) { m.y = vy; ay = k; }
+    if (vz > m.z || vz != vz) { m.z = vz; az = k; }
+    if (vw > m.w || vw != vw) { m.w = vw; aw = k; }
   }
-  if (!(m.x > 0.f)) { m.x = 0.f; ax = 15; }
-  if (!(m.y > 0.f)) { m.y = 0.f; ay = 15; }
-  if (!(m.z > 0.f)) { m.z = 0.f; az = 15; }
-  if (!(m.w > 0.f)) { m.w = 0.f; aw = 15; }
+  // the ReLU: <= 0 (and -inf) becomes +0 without a gradient; a NaN stays, with the gradient at its position
+  if (m.x <= 0.f) { m.x = 0.f; ax = 15; }
+  if (m.y <= 0.f) { m.y = 0.f; ay = 15; }
+  if (m.z <= 0.f) { m.z = 0.f; az = 15; }
+  if (m.w <= 0.f) { m.w = 0.f; aw = 15; }
   const size_t i = ((n * Ho + oh) * Wo) * C4 + col;
   out[i] = L::pack_quad(m);
   arg[i] = (unsigned short)(ax | (ay << 4) | (az << 8) | (aw << 12));

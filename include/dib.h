@@ -375,13 +375,16 @@ int dib_coco_box_iou(const double *dt_dev, const double *gt_dev, const unsigned 
  * Convolution epilogue of the ResNet-50 trunk with its frozen batch-norm folded into the weights
  * (reference models/faster_rcnn.py:367 builds the trunk with torchvision's FrozenBatchNorm2d):
  *   x = act(x + bias[c] (+ residual)), in place, channels-last fp32 (channel index fastest);
- * one pass instead of eager PyTorch's 2-4.  residual_dev may be NULL; relu != 0 applies ReLU.
+ * one pass instead of eager PyTorch's 2-4.  residual_dev may be NULL; relu != 0 applies ReLU as torch does (clamp_min(0)):
+ * a NaN goes through, everything else that is not > 0 becomes +0.  The same ReLU is in dib_bias_act_transpose, in
+ * dib_bn_mode_one_nhwc and in the bf16 forms below.
  * ------------------------------------------------------------------------------------- */
 int dib_bias_act_nhwc(float *x_dev, const float *bias_dev, const float *residual_dev, long long n_elems,
                       int C, int relu, void *stream);
 
 /* The ReLU form of the above that also leaves what its backward pass needs of the result: mask_dev[n_elems / 4],
- * one byte per 4 consecutive elements, bit k = element 4 i + k is positive (C % 4 == 0, 16-byte aligned tensors).
+ * one byte per 4 consecutive elements, bit k = element 4 i + k is > 0 -- a NaN element is stored as NaN and carries no bit
+ * (C % 4 == 0, 16-byte aligned tensors).
  * dib_relu_mask_backward: grad_out = mask ? grad_in : 0 -- torch's threshold_backward(grad, y, 0) (the ReLU backward
  * behind every trunk convolution, reference models/faster_rcnn.py:367 / torchvision Bottleneck) at 8.25 instead of
  * 12 bytes per element; grad_out may alias grad_in. */
@@ -406,8 +409,11 @@ int dib_fpn_topdown_merge_nhwc(float *x_dev, const float *bias_dev, const float 
                                void *stream);
 /* ResNet stem (torchvision resnet50: conv1 -> bn1 -> relu -> maxpool(3, stride 2, padding 1)) behind the folded convolution:
  * out[N, Ho, Wo, C] = max_pool2d(relu(x + bias)), Ho = (H - 1) / 2 + 1, in one pass; arg_dev: one unsigned short per 4 output
- * channels (4-bit window position of the winner, 15 = no gradient).  The backward pass turns grad_out + arg into the dense
- * gradient of x (max-pool backward and ReLU backward in one pass).  Channels-last fp32, C % 4 == 0, 16-byte aligned. */
+ * channels (4-bit window position of the winner, 15 = no gradient: the maximum is neither > 0 nor NaN).  ATen's selection: the
+ * first maximum in row-major window order wins; a NaN beats every number and the LAST NaN of a window is the recorded one; the
+ * pooled value of such a window is NaN (not 0) and its gradient goes to that position.  The backward pass turns grad_out + arg
+ * into the dense gradient of x (max-pool backward and ReLU backward in one pass).  Channels-last fp32, C % 4 == 0, 16-byte
+ * aligned. */
 int dib_stem_pool_forward(const float *x_dev, const float *bias_dev, float *out_dev, unsigned short *arg_dev, int N, int H, int W, int C,
                           void *stream);
 int dib_stem_pool_backward(const float *grad_out_dev, const unsigned short *arg_dev, float *grad_in_dev, int N, int H, int W, int C,

@@ -1295,3 +1295,130 @@ def labels64(match, gt_labels, ok, P):
         live[:P] = True if ok is None else np.asarray(ok)[n, :P] != 0
         out[n] = np.where(live, v, -1)
     return out
+
+
+# --------------------------------------------------------------------------------------
+# A21 trunk epilogues: float32 references for csrc/dib_eltwise_vec.h (both lane types), the scalar and the transposing
+#     kernel of csrc/dib_eltwise.hip and the apply pass of csrc/dib_bnstats.hip
+#     (torchvision's Bottleneck / FeaturePyramidNetwork / ResNet stem arithmetic between the convolutions, which
+#     reference models/faster_rcnn.py:367 builds)
+# --------------------------------------------------------------------------------------
+# Plain numpy on the host, no torch, nothing of the package.  Activations are channels-last arrays [N, H, W, C] (or flat, channel
+# fastest) of float32; every addition is ONE float32 operation in the kernels' documented order, so a correct kernel equals
+# these bit for bit (NaN by position).  tests/test_trunk_epilogue_reference.py holds them to torch on the CPU.
+
+def relu32(v):
+    """torch's relu in values -- a NaN goes through -- with the kernels' zero: every result that is not > 0 and not NaN is +0.0
+    (torch.relu on the CPU returns -0.0 for -0.0)."""
+    v = np.asarray(v)
+    return np.where((v > 0) | np.isnan(v), v, v.dtype.type(0.0))
+
+
+def bias_act32(x, bias, res=None, relu=False):
+    """bias_act_kernel / bias_act_scalar_kernel: act((x + bias[c]) + res)."""
+    with np.errstate(invalid="ignore", over="ignore"):                     # inf - inf is data here
+        v = np.asarray(x, dtype=np.float32) + np.asarray(bias, dtype=np.float32)
+        if res is not None:
+            v = v + np.asarray(res, dtype=np.float32)
+    return relu32(v) if relu else v
+
+
+def sign_mask(y, lane=4):
+    """The ReLU mask: one byte per `lane` consecutive stored elements (4 for fp32, 8 for bf16), bit k = element k > 0.  A NaN
+    carries no bit."""
+    bits = (np.asarray(y).reshape(-1, lane) > 0).astype(np.uint32)
+    return (bits << np.arange(lane, dtype=np.uint32)).sum(1).astype(np.uint8)
+
+
+def mask_bits(mask, lane=4):
+    """sign_mask's inverse: a flat bool array, one entry per element."""
+    return ((np.asarray(mask, dtype=np.uint8)[:, None] >> np.arange(lane, dtype=np.uint8)) & 1).astype(bool).reshape(-1)
+
+
+def mask_select(g, mask, lane=4):
+    """relu_mask_bwd_kernel: mask ? g : +0.0."""
+    g = np.asarray(g)
+    return np.where(mask_bits(mask, lane).reshape(g.shape), g, g.dtype.type(0.0))
+
+
+def add_relu_mask32(a, b, mask=None):
+    """add_mask_kernel: a + b, then cleared (+0.0) where the mask bit is clear; no mask: the plain sum."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.asarray(a, dtype=np.float32) + np.asarray(b, dtype=np.float32)
+    return s if mask is None else mask_select(s, mask)
+
+
+def scatter_add32(a, b, stride):
+    """scatter_add_kernel: a[n, ys * stride, xs * stride, :] += b[n, ys, xs, :]; every other element of a unchanged."""
+    out = np.array(a, dtype=np.float32, copy=True)
+    Hs, Ws = b.shape[1], b.shape[2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        out[:, 0:(Hs - 1) * stride + 1:stride, 0:(Ws - 1) * stride + 1:stride, :] += np.asarray(b, dtype=np.float32)
+    return out
+
+
+def nearest_src(out_size, in_size):
+    """ATen's nearest-neighbour source index (upsample_nearest2d with an output size): min(int(floorf(dst * scale)), in - 1)
+    with scale = float32(in) / float32(out), the product in float32."""
+    scale = np.float32(in_size) / np.float32(out_size)
+    dst = np.arange(out_size, dtype=np.float32)
+    return np.minimum(np.floor(dst * scale).astype(np.int64), in_size - 1)
+
+
+def topdown_merge32(x, bias, top):
+    """topdown_merge_kernel: (x + bias[c]) + top[n, sh(h), sw(w), :]."""
+    H, W = x.shape[1], x.shape[2]
+    sh, sw = nearest_src(H, top.shape[1]), nearest_src(W, top.shape[2])
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.asarray(x, dtype=np.float32) + np.asarray(bias, dtype=np.float32)
+        return v + np.asarray(top, dtype=np.float32)[:, sh][:, :, sw]
+
+
+def stem_pool32(x, bias):
+    """stem_pool_fwd_kernel: relu32(x + bias), then the 3 x 3 / stride 2 / padding 1 maximum with ATen's selection: the first
+    maximum in row-major window order wins, a NaN beats everything and the LAST NaN of a window wins.  Returns the pooled values
+    [N, Ho, Wo, C] float32 and the winner's window position 0..8 (uint8; 15 where the maximum is not > 0 and not NaN: no
+    gradient)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = relu32(np.asarray(x, dtype=np.float32) + np.asarray(bias, dtype=np.float32))
+    N, H, W, C = y.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    pad = np.full((N, 2 * Ho + 2, 2 * Wo + 2, C), -np.inf, dtype=np.float32)
+    pad[:, 1:H + 1, 1:W + 1] = y
+    m = np.full((N, Ho, Wo, C), -np.inf, dtype=np.float32)
+    pos = np.full((N, Ho, Wo, C), 15, dtype=np.uint8)
+    for k in range(9):
+        v = pad[:, k // 3:k // 3 + 2 * Ho:2, k % 3:k % 3 + 2 * Wo:2]
+        take = (v > m) | np.isnan(v)
+        m = np.where(take, v, m)
+        pos = np.where(take, np.uint8(k), pos)
+    dead = ~(m > 0) & ~np.isnan(m)
+    return np.where(dead, np.float32(0.0), m), np.where(dead, np.uint8(15), pos)
+
+
+def pack_pool_arg(pos):
+    """The kernels' `arg`: one uint16 per 4 consecutive channels, 4 bits per channel, channel 4 i in the low nibble."""
+    p = np.asarray(pos, dtype=np.uint16).reshape(-1, 4)
+    return (p[:, 0] | (p[:, 1] << 4) | (p[:, 2] << 8) | (p[:, 3] << 12)).astype(np.uint16)
+
+
+def stem_pool_backward64(gout, pos, H, W):
+    """stem_pool_bwd_kernel: the pooled gradient goes to the recorded position (none for 15); an input pixel sums the at most
+    four windows it won, here in float64."""
+    gout = np.asarray(gout, dtype=np.float64)
+    N, Ho, Wo, C = gout.shape
+    pad = np.zeros((N, 2 * Ho + 2, 2 * Wo + 2, C), dtype=np.float64)
+    for k in range(9):
+        pad[:, k // 3:k // 3 + 2 * Ho:2, k % 3:k % 3 + 2 * Wo:2] += np.where(pos == k, gout, 0.0)
+    return pad[:, 1:H + 1, 1:W + 1]
+
+
+def to_bf16_bits(v):
+    """float32 -> bfloat16 bit patterns (uint16), round to nearest even; NaN stays NaN, +-inf stays."""
+    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    return np.where(np.isnan(v), np.uint16(0x7FC0), r)
+
+
+def from_bf16_bits(b):
+    return (np.asarray(b, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)

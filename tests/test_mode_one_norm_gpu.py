@@ -1,5 +1,6 @@
 """`--mode_one_norm` on the MI355X: the HIP path of models/batchnorm.BatchNorm2d (csrc/dib_bnstats.hip) against float64 on the
 53 trunk shapes at batch 1, 800 x 1344 (and N = 2), against the fixture's reference outputs, and bitwise against itself; the
+same bounds on small shapes that reach every branch of the launch geometry, and a NaN that stays in its channel; the
 converted detector (every layer on the HIP path, close to the torch path, graphed == eager, conversion after a frozen
 evaluation == a fresh conversion); and evaluate.main --mode_one_norm reproducible across two fresh processes."""
 import copy
@@ -140,6 +141,92 @@ def test_num_batches_tracked_on_the_host_or_the_device():
     bn.num_batches_tracked = bn.num_batches_tracked.cpu()
     b = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last))
     assert torch.equal(a, b)
+
+
+# ---- launch geometry between the fixture's tiny cases and the trunk shapes, and a NaN ---------------------------------------------
+
+# (C, npix) chosen from bn_geometry (csrc/dib_bnstats.hip) so that every branch of it is reached; R = pixel rows per workgroup,
+# QB = channel quads per workgroup, S = pixel slices
+GEOMETRY = [(4, 1), (4, 1023), (4, 4096), (4, 8195),      # R = 1024: one pixel; idle rows; S = 1 exactly; S = 2 with uneven slices
+            (12, 2731),                                    # QB = 3, R = 341: lane 1023 idle; S = 2
+            (260, 197),                                    # two channel chunks, the second with one live quad; S = 3
+            (64, 16401), (64, 16643), (64, 65791)]         # S = 64, 65 (the finalize batch boundary) and the cap of 256
+
+
+def _relu_keeping_nan(y):
+    """the ReLU of the epilogue references, oracle/dib_oracle.py relu32 itself (numpy, on the host)"""
+    import dib_oracle as O
+    return torch.from_numpy(O.relu32(y.cpu().numpy())).to(y.device)
+
+
+def _geometry_input(C, npix, dev, seed):
+    """[1, C, npix, 1] channels-last: _activation's channels, with channel 0 constant (batch variance exactly 0), channel 1 a
+    narrow channel with one outlier and, for npix <= 8195, channel 2 at |mean| ~ 1e3 sigma.  The kernel reports the MIXED
+    statistics only (16/17 running + 1/17 batch), so the zero batch variance is checked through that mix: an error e of the
+    batch variance shows as e / 17 against a bound of 1e-5 of the mixed variance."""
+    x = _activation(1, C, npix, 1, dev, seed)
+    g = torch.Generator(device=dev).manual_seed(seed + 1)
+    x[:, 0] = 3.25
+    x[:, 1] = torch.randn((1, npix, 1), generator=g, device=dev) * 0.01
+    x[0, 1, npix // 3, 0] = 1000.0
+    if npix <= 8195:
+        x[:, 2] = torch.randn((1, npix, 1), generator=g, device=dev) + 1000.0
+    return x
+
+
+def _check_against_float64(bn, x, res, relu_on, channels=None, what=None):
+    stats = torch.empty((2, x.shape[1]), dtype=torch.float32, device=x.device)
+    y = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last), res, relu_on, stats)
+    y2 = bn._mode_one_hip_(x.clone(memory_format=torch.channels_last), res, relu_on)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        mean64, var64, y64 = _f64(bn, x, res, False)
+    if relu_on:
+        y64 = _relu_keeping_nan(y64)
+    c = slice(None) if channels is None else channels
+    assert torch.equal(y[:, c], y2[:, c]), "two calls on the same input differ"
+    sd = var64.sqrt()
+    em = ((stats[0].double() - mean64).abs() / (1e-5 * sd + 2.4e-7 * mean64.abs()))[c]
+    ev = ((stats[1].double() - var64).abs() / (1e-5 * var64))[c]
+    ey = ((y.detach().double() - y64).abs() / (1 + y64.abs()))[:, c]
+    print("%s: mean error / bound %.3f (channel %d), variance error / bound %.3f (channel %d), output error %.2e"
+          % (what, float(em.max()), int(em.argmax()), float(ev.max()), int(ev.argmax()), float(ey.max())))
+    assert float(em.max()) <= 1, (what, "mean", em.tolist()[:4])
+    assert float(ev.max()) <= 1, (what, "variance", ev.tolist()[:4])
+    assert float(ey.max()) <= 1e-4, (what, float(ey.max()))
+    return stats, y
+
+
+@pytest.mark.parametrize("C,npix", GEOMETRY, ids=lambda v: str(v))
+def test_kernel_against_float64_across_the_launch_geometry(C, npix):
+    """The file's bounds (mean 1e-5 sigma + 2.4e-7 |mean|, variance 1e-5 relative, output 1e-4 (1 + |y|)) on every branch of the
+    partial-statistics geometry, with and without residual and ReLU, including a constant, a one-outlier and a large-mean channel."""
+    dev = torch.device("cuda")
+    bn = _layer(C, dev, C + npix % 97)
+    x = _geometry_input(C, npix, dev, 7 * C + npix % 89)
+    r = _activation(1, C, npix, 1, dev, 11 * C + npix % 83)
+    for res_on in (False, True):
+        for relu_on in (False, True):
+            _check_against_float64(bn, x, r if res_on else None, relu_on, what="C %d, %d pixels%s%s" % (C, npix, ", residual" if res_on else "", ", relu" if relu_on else ""))
+
+
+def test_a_nan_poisons_its_channel_only_and_passes_the_relu():
+    """C = 8, 63 pixels, a single NaN in channel 5: channel 5 of the output is NaN everywhere, with the ReLU on and off (torch's relu
+    keeps a NaN), its statistics are NaN; the other channels -- the three that share channel 5's float4 included -- stay within
+    the bounds."""
+    dev = torch.device("cuda")
+    C, npix = 8, 63
+    bn = _layer(C, dev, 5)
+    x = _activation(1, C, 7, 9, dev, 6)
+    x[0, 5, 3, 4] = float("nan")
+    r = _activation(1, C, 7, 9, dev, 8)
+    others = [0, 1, 2, 3, 4, 6, 7]
+    for res_on in (False, True):
+        for relu_on in (False, True):
+            stats, y = _check_against_float64(bn, x, r if res_on else None, relu_on, channels=others, what="NaN case, relu %d, residual %d" % (relu_on, res_on))
+            assert bool(torch.isnan(stats[:, 5]).all()), stats[:, 5]
+            assert bool(torch.isnan(y[:, 5]).all()), (relu_on, int(torch.isnan(y[:, 5]).sum()), npix)
+            assert not bool(torch.isnan(y[:, others]).any())
 
 
 # ---- the converted detector ----------------------------------------------------------------------------------------------------------

@@ -81,11 +81,38 @@ def test_train_cli_with_stored_psfs_end_to_end(tmp_path, capsys):
     args = train.build_parser().parse_args([
         "--synthetic", "--synthetic_images", "4", "--synthetic_size", "160", "224", "--blur_train", "--gpu_blur",
         "--use_stored_psfs", "--stored_psf_directory", dest + "psfs", "--stored_psf_count", "2", "--param_index", "1",
-        "--low_exposure", "--expand_target_boxes", "--use_custom_image_norm", "-b", "2", "--epochs", "1", "--early_stop", "2",
+        "--low_exposure", "--expand_target_boxes", "-b", "2", "--epochs", "1", "--early_stop", "2",
         "--lr", "0.002", "--print_freq", "1", "--output_dir", out, "--tensorboard_path", str(tmp_path / "tb")])
+    # without --use_custom_image_norm: with stored PSFs the reference's blur dictionary carries param_index - 1 of the nearest-type
+    # bin (transforms.py:427-428), here -1, for which get_norm_params keeps an all-zero std row (utils.py:219-273): the normalised
+    # batch is inf / NaN in every pixel and the reference's step ends in "Loss is nan, stopping training" -- as this one does since
+    # the trunk's fused ReLUs let a NaN through (tests/test_trunk_epilogue_f32_gpu.py)
     train.main(args)
     text = capsys.readouterr().out
     assert "loss_classifier" in text and "nan" not in text.lower().split("namespace")[-1]
+
+
+def test_train_cli_with_stored_psfs_and_custom_norm_stops_at_the_nan_loss_like_the_reference(tmp_path, capsys):
+    """The flags of the test above plus --use_custom_image_norm.  With stored PSFs the blur dictionary carries param_index - 1 of
+    the nearest-type bin (reference transforms.py:427-428), here -1, for which get_norm_params keeps an all-zero std row (reference
+    utils.py:249-268): every pixel of a blurred image is normalised to inf or NaN.  The reference's plain-torch trunk carries that to
+    the loss and its loop stops at the step (engine.py:145-148); so does this one, now that the trunk's fused ReLUs let a NaN
+    through -- with fmaxf(v, 0) they erased it and the run trained on with finite losses."""
+    from detectinblur_amd import train, utils
+    from detectinblur_amd.dataset_utils import generate_PSFs as G
+    stds = utils.get_norm_params([{"blurring": True, "param_index": -1, "fraction_index": 1}], True)[1]
+    assert (stds == 0).all()
+    dest = str(tmp_path) + "/"
+    G.main(G.get_parser().parse_args(["--destination_path", dest, "--num_workers", "1", "--total_num_psfs", "2", "--packed"]))
+    args = train.build_parser().parse_args([
+        "--synthetic", "--synthetic_images", "4", "--synthetic_size", "160", "224", "--blur_train", "--gpu_blur",
+        "--use_stored_psfs", "--stored_psf_directory", dest + "psfs", "--stored_psf_count", "2", "--param_index", "1",
+        "--low_exposure", "--expand_target_boxes", "--use_custom_image_norm", "-b", "2", "--epochs", "1", "--early_stop", "2",
+        "--lr", "0.002", "--print_freq", "1", "--output_dir", str(tmp_path / "run"), "--tensorboard_path", str(tmp_path / "tb")])
+    with pytest.raises(SystemExit) as stop:
+        train.main(args)
+    assert stop.value.code == 1
+    assert "Loss is nan, stopping training" in capsys.readouterr().out
 
 
 def test_evaluate_cli_ensemble_sweep_end_to_end(capsys, tmp_path):
