@@ -22,6 +22,7 @@ DIB_EINVAL, DIB_ESHAPE, DIB_EHIP, DIB_ENOT128, DIB_ECAPTURE, DIB_ETIMEOUT = -1, 
 DIB_STEP_PSFS_COMPLETE, DIB_STEP_LARGE_WINDOW = 1, 2
 DIB_COMPACT_LARGE_WINDOW, DIB_WINDOW_LARGE, DIB_COMPACT_VRUNS = 8, 0x100, 16
 DIB_EPILOGUE_QUANTIZE, DIB_EPILOGUE_PAD = 1, 2
+DIB_WARP_NHWC, DIB_WARP_NCHW = 0, 1
 
 _lib = None
 
@@ -148,6 +149,10 @@ _SIGNATURES = {
     "dib_augmix_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_ulonglong]),
     "dib_augmix": (ctypes.c_int, [_c_augmix_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "dib_squint_warp_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_squint_warp_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # test hook, not part of the drop-in boundary
     "dib_sparse_blur_generic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

@@ -16,7 +16,7 @@ class GeneralizedRCNN(nn.Module):
         self.warp_internally = warp_internally
         if warp_internally:
             from .warper import Warper
-            self.warper = Warper()
+            self.warper = Warper(fused=True)         # one HIP launch per warp on the GPU (csrc/dib_warp.hip); torch's op chain elsewhere
         # Inference through a HIP graph of the static trunk (backbone + FPN + RPN head + proposal filtering): off by
         # default, switched on by engine.evaluate on a GPU (graphs.py).  Same kernels, same results, ~300 launches fewer
         # for the interpreter per image.
@@ -34,6 +34,51 @@ class GeneralizedRCNN(nn.Module):
         # travels with the outputs so that the StaticGraph keeps it alive after the cache has moved on to another geometry
         return tuple(fl) + tuple(self.rpn.propose_static(fl, anchors, self._sizes[x.shape[0]])) + (anchors,)
 
+    # ---- the trunk of a model that warps internally ("squint", forward's eager branch below) as a capturable function ----------
+    # The fused warp reads its Half matrices from device memory when it runs, so a captured trunk follows whatever its matrix
+    # buffers hold at replay.  squint_matrices calls torch.inverse, which must not be captured: the matrices are computed eagerly
+    # -- one set per warped tensor's geometry, as forward's eager branch computes them (the last bits of the float32 inverses can
+    # depend on the width and height that the reference puts into the matrix), so that a replay equals the eager result bit
+    # for bit -- and copied into static buffers (kept like `_sizes`: never reallocated) keyed by (batch size, H, W, inverse
+    # scales).  Outside a capture the trunk fills the buffers of the tensors it meets and notes them per input shape; before a
+    # replay `_fill_warp_mats` refreshes the noted ones.
+    def _fill_warp_mats(self, key):
+        from .warper import squint_matrices
+        _, H, W, inverse = key
+        thetas, l1, l2 = self._warp_params
+        if inverse:
+            l1, l2 = 1 / l1, 1 / l2
+        self._warp_mats[key].copy_(squint_matrices(thetas, l1, l2, W, H))
+
+    def _warp_static(self, t, inverse, plan):
+        from .warper import squint_warp_launch
+        key = (t.shape[0], t.shape[2], t.shape[3], inverse)
+        mats = self.__dict__.setdefault("_warp_mats", {})
+        if key not in mats:
+            mats[key] = torch.zeros((t.shape[0], 2, 3), dtype=torch.float16, device=t.device)
+        if not torch.cuda.is_current_stream_capturing():
+            self._fill_warp_mats(key)
+            if key not in plan:
+                plan.append(key)
+        return squint_warp_launch(t, mats[key])
+
+    def _trunk_warped(self, x):
+        plan = self.__dict__.setdefault("_warp_plans", {}).setdefault(tuple(x.shape), [])
+        warped, tables = self._warp_static(x, False, plan)
+        feats = self.backbone(warped)
+        if isinstance(feats, torch.Tensor):
+            feats = OrderedDict([("0", feats)])
+        self._feat_names = list(feats.keys())
+        fl = []
+        for f in feats.values():
+            f, t = self._warp_static(f, True, plan)
+            fl.append(f)
+            tables += t
+        from .net_transforms import ImageList
+        anchors = self.rpn.anchor_generator(ImageList(x, [None] * x.shape[0]), fl)[0]
+        # anchors and the warps' base-coordinate tables are read through raw pointers: they travel with the outputs (see _trunk)
+        return tuple(fl) + tuple(self.rpn.propose_static(fl, anchors, self._sizes[x.shape[0]])) + (anchors,) + tuple(tables)
+
     def _sync_graphs_with_weights(self, cache):
         """A captured trunk reads the FPN / RPN parameters through their live pointers and the trunk's convolutions through the
         cached batch-norm folds (backbone._folded).  Before every replay: (1) if any parameter or buffer of the trunk was
@@ -50,13 +95,15 @@ class GeneralizedRCNN(nn.Module):
         if self.__dict__.get("_trunk_ptrs") != ptrs:
             if "_trunk_ptrs" in self.__dict__:
                 cache.clear()
+                self.__dict__.get("_warped_trunk_graphs", cache).clear()      # the plain and the warped trunk read the same weights
+                self.__dict__.get("_trunk_graphs", cache).clear()
                 self.__dict__.pop("_trunk_tensors")         # parameters may have been re-registered
             for key in ("_dib_fold_watch", "_dib_fold_state"):      # refresh_folded's shortcut watches the old tensors
                 self.backbone.__dict__.pop(key, None)
             self.__dict__["_trunk_ptrs"] = ptrs
         refresh_folded(self.backbone)
 
-    def _forward_graphed(self, images, original_sizes):
+    def _forward_graphed(self, images, original_sizes, warp_params=None):
         from ..graphs import GraphCache
         x = images.tensors
         n = x.shape[0]
@@ -65,9 +112,17 @@ class GeneralizedRCNN(nn.Module):
             sizes[n] = torch.zeros((n, 2), dtype=x.dtype, device=x.device)       # read by the captured graph: never reallocated
         host = torch.tensor([[float(s[1]), float(s[0])] for s in images.image_sizes], dtype=x.dtype).pin_memory()
         sizes[n].copy_(host, non_blocking=True)
-        cache = self.__dict__.get("_trunk_graphs")
-        if cache is None:
-            cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk)
+        if warp_params is None:
+            cache = self.__dict__.get("_trunk_graphs")
+            if cache is None:
+                cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk)
+        else:
+            cache = self.__dict__.get("_warped_trunk_graphs")
+            if cache is None:
+                cache = self.__dict__["_warped_trunk_graphs"] = GraphCache(self._trunk_warped)
+            self.__dict__["_warp_params"] = warp_params
+            for key in self.__dict__.get("_warp_plans", {}).get(tuple(x.shape), ()):
+                self._fill_warp_mats(key)
         self._sync_graphs_with_weights(cache)
         outs = cache(x)
         hook = self.__dict__.pop("_after_trunk_launch", None)
@@ -75,8 +130,9 @@ class GeneralizedRCNN(nn.Module):
             # engine.evaluate's look-ahead: the trunk is queued, the host is about to wait for it -- the moment to queue the next
             # image's blur / estimator pass and the upload of the one after (one call per forward pass, then forgotten)
             hook()
-        features = OrderedDict(zip(self._feat_names, outs[:-4]))
-        proposals, _ = self.rpn.unpad(*outs[-4:-1])
+        nf = len(self._feat_names)                 # outs: the levels, propose_static's three, then what the graph keeps alive
+        features = OrderedDict(zip(self._feat_names, outs[:nf]))
+        proposals, _ = self.rpn.unpad(*outs[nf:nf + 3])
         detections, _ = self.roi_heads(features, proposals, images.image_sizes, None)
         return self.transform.postprocess(detections, images.image_sizes, original_sizes)
 
@@ -167,9 +223,11 @@ class GeneralizedRCNN(nn.Module):
                     raise ValueError("Expected target boxes to be a tensor" "of shape [N, 4], got {:}.".format(boxes.shape))
         original_sizes = [(int(img.shape[-2]), int(img.shape[-1])) for img in images]
         images, targets = self.transform(images, targets, newMeans, newSTDs)
-        if (self.graph_inference and not self.training and targets is None and not torch.is_grad_enabled() and images.tensors.is_cuda
-                and not (self.warp_internally and not killWarp)):
-            return self._forward_graphed(images, original_sizes)
+        if self.graph_inference and not self.training and targets is None and not torch.is_grad_enabled() and images.tensors.is_cuda:
+            if not (self.warp_internally and not killWarp):
+                return self._forward_graphed(images, original_sizes)
+            if self.warper.takes_fused(images.tensors):
+                return self._forward_graphed(images, original_sizes, (thetas, lambda1s, lambda2s))
         # degenerate-box check (reference generalized_rcnn.py:119-129).  The flag is computed on the device right here
         # and copied to pinned host memory behind the transform; it is READ only once the whole forward pass has been
         # enqueued, after waiting for that copy alone -- the GPU reaches it before it starts the backbone, so the host

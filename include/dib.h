@@ -541,6 +541,30 @@ int dib_augmix(const dib_augmix_image *plans_host, const dib_augmix_image *plans
                const double *scale_table_dev, const unsigned short *half_table_dev, void *workspace_dev, size_t workspace_bytes,
                void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * "Squint" warp, the reference's `--warp_in_model` (models/warper.py:47-50: Half affine_grid + bilinear grid_sample, zeros
+ * outside, align_corners False) as one launch on fp32 activations, with no grid tensor and no Half copy of the input.
+ * Per output pixel (n, i, j), with m = mats_dev[n] (Half [2][3], READ ON THE DEVICE: a captured graph sees the values its
+ * buffer holds at replay), bx = base_x_dev[j], by = base_y_dev[i] (Half tables: torch's own base grid,
+ * linspace(-1, 1, W) * (W - 1) / W in Half, built by the caller -- the closed form does not reproduce its rounding):
+ *   gx = half((m00 * bx + m01 * by) + m02),  gy = half((m10 * bx + m11 * by) + m12)       fp32, left to right, one rounding to Half
+ *   ix = ((gx + 1) * W - 1) / 2,  iy = ((gy + 1) * H - 1) / 2                             fp32
+ *   out = sum over the four corners (floor(ix) + {0, 1}, floor(iy) + {0, 1}) INSIDE the image of weight * in[corner]
+ * A corner inside the image is multiplied and added even at weight 0 (a NaN / inf pixel reaches the output where torch's
+ * grid_sample lets it); a corner outside is skipped.  The fp32 sum is stored as is (the reference rounds it to Half once more).
+ * layout: DIB_WARP_NHWC (element order N, H, W, C; C % 4 == 0 with 16-byte aligned in / out: four channels per lane) or
+ * DIB_WARP_NCHW (planar).  out must not alias in.  The backward pass ADDS the input gradient of the same warp into
+ * grad_in_dev (zero-filled by the caller) with float atomic adds, one lane per element of grad_out: its sums depend on arrival
+ * order in the last bits.  No gradient for the matrices or tables.  No host synchronisation: capturable into a graph.
+ * ------------------------------------------------------------------------------------- */
+#define DIB_WARP_NHWC 0
+#define DIB_WARP_NCHW 1
+int dib_squint_warp_forward(const float *in_dev, float *out_dev, int N, int C, int H, int W, int layout, const unsigned short *mats_dev,
+                            const unsigned short *base_x_dev, const unsigned short *base_y_dev, void *stream);
+int dib_squint_warp_backward(const float *grad_out_dev, float *grad_in_dev, int N, int C, int H, int W, int layout,
+                             const unsigned short *mats_dev, const unsigned short *base_x_dev, const unsigned short *base_y_dev,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
