@@ -40,6 +40,11 @@ class AugmixImage(ctypes.Structure):
 
 _c_augmix_p = ctypes.POINTER(AugmixImage)
 
+
+class OverlayBox(ctypes.Structure):
+    """include/dib.h dib_overlay_box: one outline of dib_overlay_rgb8 (rgb = R | G << 8 | B << 16 of the output)."""
+    _fields_ = [("x0", ctypes.c_int), ("y0", ctypes.c_int), ("x1", ctypes.c_int), ("y1", ctypes.c_int), ("rgb", ctypes.c_uint)]
+
 _SIGNATURES = {
     "dib_abi_version": (ctypes.c_int, []),
     "dib_last_error": (ctypes.c_char_p, []),
@@ -153,6 +158,8 @@ _SIGNATURES = {
                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dib_squint_warp_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_overlay_rgb8": (ctypes.c_int, [_c_void_pp, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int, ctypes.c_void_p, _c_int_p, _c_void_pp,
+                                        ctypes.c_void_p]),
     # test hook, not part of the drop-in boundary
     "dib_sparse_blur_generic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

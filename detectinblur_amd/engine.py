@@ -465,7 +465,12 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     """reference engine.py:220-416.  Runs the detector (or the routed ensemble) over the loader, scores the
     detections against the dataset's COCO ground truth (boxes replaced by the expanded ones under
     `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
-    `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
+    `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES.
+    `image_output_folder` (reference :382-383): when given, every evaluated image is written as `<folder>/img<count>.png` -- the first
+    image of the batch as the detector gets it (after blur and corruptions), with the outline of every detection above 0.5
+    (overlay.py); `count` is the loop's index.  With more than one rank the files go to `<folder>/rank<r>/` (the reference lets the
+    ranks overwrite each other).  On a GPU the picture is rendered by one HIP launch on the writer's stream and encoded on worker
+    threads: no synchronisation is added to the loop."""
     from .blur_ops import acc_mode_constant
     from .coco_eval import CocoEvaluator
     from .coco_utils import get_coco_api_from_dataset
@@ -510,7 +515,39 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         def score(res):           # the box-IoU kernel of the matching on its own stream: never queued behind the detector
             with torch.cuda.stream(score_stream):
                 coco_evaluator.update(res)
+    png_writer = None
     try:
+        if image_output_folder is not None:
+            from . import overlay
+            folder = str(image_output_folder)
+            if utils.get_world_size() > 1:
+                folder = os.path.join(folder, "rank%d" % utils.get_rank())
+            png_writer = overlay.PngWriter(folder)
+
+        def picture_of(images_GPU, index):
+            """What `submit` needs to save image `index`'s picture: the first image of the batch as it stands now (the caller has just
+            synchronised: it is complete), an event that says so to the writer's stream, and the loop's index."""
+            if png_writer is None:
+                return None
+            image, complete = images_GPU[0], None
+            if image.is_cuda:
+                complete = torch.cuda.Event()
+                complete.record()
+            return image, complete, index
+
+        def save_picture(picture, output):
+            image, complete, index = picture
+            if not image.is_cuda:
+                overlay.save_png(png_writer.path(index), overlay.render_host(image, output["boxes"], output["labels"], output.get("scores")))
+                return
+            # render and copy on the writer's stream, behind the event; nothing here waits for the device (a full ring of
+            # pictures still being encoded does hold the loop: PngWriter.submit)
+            stream = png_writer.stream(image.device)
+            stream.wait_event(complete)
+            image.record_stream(stream)
+            with torch.cuda.stream(stream):
+                png_writer.submit(index, overlay.render_device([image], [output], stream=stream)[0])
+
         # On a GPU the loop works one batch ahead (_StagedAhead): while the host waits for the detections of image i, image i + 1's
         # blur, box growth and blur-estimator pass are already queued, and image i + 2's upload runs on the side stream.  Only
         # work without host random draws goes ahead (--add_noise / --add_block / --add_jpeg_artefacts draw in `blur_image_list`).
@@ -530,8 +567,10 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 est = _estimate(blur_estimator, batched.tensors, graphed)
             return images_GPU, targets_GPU, blur_dicts, thetas, l1, l2, est
 
-        def submit(ids, outputs, gt_xywh, started):
-            """detections of one batch (CPU tensors) -> result tables + the evaluator (reference :376-392)"""
+        def submit(ids, outputs, gt_xywh, started, picture=None):
+            """detections of one batch (CPU tensors) -> result tables + the evaluator (reference :376-392); `picture`: picture_of()"""
+            if picture is not None:
+                save_picture(picture, outputs[0])                            # reference :382-383, inside model_time there too
             model_time = time.time() - started
             res = {}
             for image_id, o, g in zip(ids, outputs, gt_xywh):
@@ -546,8 +585,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             metric_logger.update(model_time=model_time, evaluator_time=time.time() - evaluator_time)
 
         def finalize(entry):
-            core_, handle_, ids_, gt_, started_ = entry
-            submit(ids_, core_.finish(handle_), gt_, started_)
+            core_, handle_, ids_, gt_, started_, picture_ = entry
+            submit(ids_, core_.finish(handle_), gt_, started_, picture_)
 
         # models whose internal warp is on need thetas / lambdas in forward: they stay on the plain loop
         pipelined = (graphed and not os.environ.get("DIB_NO_PIPELINE")
@@ -577,6 +616,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             if device.type == "cuda":
                 torch.cuda.synchronize()
             model_time = time.time()
+            picture = picture_of(images_GPU, count)
             if expand_target_boxes and blurring_images:
                 # the expanded boxes replace the ground truth's, annotation k <- target box k (reference :325-342,
                 # index-wise: where the target dropped a crowd / degenerate annotation the tail keeps its box)
@@ -623,7 +663,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                     trunk_running = None
                 handle = core.launch_trunk(images_GPU, killWarp=not blurring_images, newMeans=norm_means, newSTDs=norm_stds)
                 if handle is not None:
-                    trunk_running = (core, handle, ids, gt_host, model_time)
+                    trunk_running = (core, handle, ids, gt_host, model_time, picture)
                     ahead.advance(more=more)
                     for entry in ready:
                         finalize(entry)
@@ -645,7 +685,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 if hooked and core.__dict__.pop("_after_trunk_launch", None) is not None:
                     ahead.advance(more=more)                                  # the forward pass took a path without the hook
                 outputs = [{k: v.to("cpu") for k, v in t.items()} for t in outputs]
-                submit(ids, outputs, [utils.convert_to_xywh(t["boxes"]).cpu() for t in targets_GPU], model_time)
+                submit(ids, outputs, [utils.convert_to_xywh(t["boxes"]).cpu() for t in targets_GPU], model_time, picture)
             count += 1
             if early_stop is not None and count > early_stop:
                 break
@@ -654,6 +694,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         if scorer is not None:
             scorer.shutdown(wait=True)
         torch.set_num_threads(n_threads)
+        if png_writer is not None:
+            png_writer.close()                                           # drains the encoders; re-raises the first error one of them hit
     for f in pending:
         f.result()                                                       # re-raises anything the scoring thread hit
     metric_logger.synchronize_between_processes()

@@ -5,7 +5,11 @@ or by the ground-truth blur_dict, over the blur sweep P in {0.005, 0.001, 0.0000
 DistributedSampler, batch size 1 per rank as in the reference.  `--vanilla_eval` scores clean images once
 (reference :226-262).  Every pass returns the reference's CocoEvaluator surface and logs its statistics to
 TensorBoard under the reference's tags.  Random-initialised models stand in for checkpoints when no paths are
-given (synthetic throughput runs).  The reference README's command lines parse unchanged."""
+given (synthetic throughput runs).  The reference README's command lines parse unchanged.
+`--save_images` (this repo) writes the reference's detection overlays (reference engine.py:382-383) under `--image_output_dir`: one
+subfolder per pass -- `clean` for the vanilla pass, `P<param>_E<fraction>` for each sweep cell (the reference hands every pass the
+same folder, so its 15 cells overwrite one another's img<count>.png; and it always writes, where this needs the flag)."""
+import os
 import argparse
 
 import torch
@@ -36,6 +40,8 @@ def build_parser():
     p.add_argument("--LEHE", action="store_true", help="System with low and high exposure networks.")
     p.add_argument("--dilate_psf", action="store_true", help="Dilate PSF to simulate defocus with motion blur.")
     p.add_argument("--model_path", default=None, help="(this repo) alias of --resume")
+    p.add_argument("--save_images", action="store_true", help="(this repo) write every evaluated image with its detections above 0.5 "
+                   "as <image_output_dir>/<pass>/img<count>.png (<pass>: clean, or P<param>_E<fraction> per sweep cell)")
     # outside the built path: accepted, refused when set
     p.add_argument("--blurred_dataset", action="store_true", help="(not built) real-blur datasets")
     p.add_argument("--expand_synth_boxes", action="store_true", help="(not built) real-blur datasets")
@@ -104,11 +110,15 @@ def main(args):
                                            pin_memory=device.type == "cuda", worker_init_fn=_seed_worker, multiprocessing_context=mp_ctx)
 
     ens_kw = dict(use_ensemble=args.use_ensemble, ensemble_models=ensemble, blur_estimator=estimator, LEHE=args.LEHE)
+
+    def pictures(name):
+        """the folder one pass writes its pictures to: None (nothing is written) without --save_images"""
+        return os.path.join(args.image_output_dir, name) if getattr(args, "save_images", False) else None
     results = {}
     if args.vanilla_eval:                                               # reference evaluate.py:226-262
         ce = evaluate(model, loader_for(get_transform(False, blur=False)), device=device, vanilla_eval=True,
                       distributed_mode=args.distributed, use_custom_image_norm=args.use_custom_image_norm,
-                      early_stop=args.early_stop, **ens_kw)
+                      early_stop=args.early_stop, image_output_folder=pictures("clean"), **ens_kw)
         log_coco_stats(writer, "Clean", ce, 0)
         if writer is not None:
             writer.close()
@@ -126,7 +136,8 @@ def main(args):
             out = evaluate(model, loader_for(tf), device=device, distributed_mode=args.distributed, early_stop=args.early_stop,
                            blurring_images=True, gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                            use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
-                           add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode, **ens_kw)
+                           add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode,
+                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **ens_kw)
             results["P%dE%d" % (param_index, fraction_index - 1)] = out
             if utils.is_main_process():
                 log_coco_stats(writer, "P" + str(param_index), out, fraction_index)

@@ -5,6 +5,8 @@
   * collate_fn, distributed helpers, meters      reference utils.py:474-785  (below)
   * convert_to_custom_batch_norm, set_batch_norm_N, set_batch_norm_mode1
                                                  reference utils.py:59-77, :122-135, :150-162 (--mode_one_norm)
+  * create_unique_color_float, compute_colors_for_labels, overlay_boxes_torch
+                                                 reference utils.py:279-353  (detection overlays: overlay.py, HIP on a GPU)
 """
 import numpy as np
 import os
@@ -12,6 +14,7 @@ import os
 import torch
 
 from . import blur_ops
+from .overlay import compute_colors_for_labels, create_unique_color_float  # noqa: F401  (reference utils.py:279-320)
 
 # ---------------------------------------------------------------------------------------------
 # test-time batch-norm (--mode_one_norm)
@@ -134,6 +137,20 @@ def fix_bounding_box_squeeze(target, image_shape):
     if work is not boxes:
         boxes.copy_(work)
     return target
+
+
+def overlay_boxes_torch(image_GPU, predictions):
+    """reference utils.py:322-353: the image (3 x H x W, float or Half) with the outline of every prediction whose score is above
+    0.5 (every prediction when there are no scores), as the H x W x 3 BGR uint8 array the reference returns -- engine.py:383
+    converts it to RGB before saving.  One HIP launch for a CUDA image (overlay.render_device), the host restatement otherwise; the
+    outline rule is include/dib.h's reading of cv2.rectangle(thickness=2), not pinned against cv2."""
+    from . import overlay
+    if image_GPU.is_cuda:
+        cpu = {k: v.cpu() for k, v in predictions.items() if k in ("boxes", "labels", "scores")}
+        rgb = overlay.render_device([image_GPU], [cpu])[0].cpu().numpy()
+    else:
+        rgb = overlay.render_host(image_GPU, predictions["boxes"], predictions["labels"], predictions.get("scores"))
+    return rgb[:, :, ::-1].copy()
 
 
 def convert_to_xywh(boxes):

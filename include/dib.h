@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes, the bf16 epilogues dib_bias_act_bf16_nhwc, dib_bias_act_mask_bf16_nhwc, dib_relu_mask_backward_bf16, dib_add_relu_mask_bf16, dib_scatter_add_bf16_nhwc, dib_fpn_topdown_merge_bf16_nhwc, dib_stem_pool_forward_bf16 / _backward_bf16): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
+#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes, the bf16 epilogues dib_bias_act_bf16_nhwc, dib_bias_act_mask_bf16_nhwc, dib_relu_mask_backward_bf16, dib_add_relu_mask_bf16, dib_scatter_add_bf16_nhwc, dib_fpn_topdown_merge_bf16_nhwc, dib_stem_pool_forward_bf16 / _backward_bf16, dib_squint_warp_forward / _backward, dib_overlay_rgb8): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
                              per-tap offset array (sizes come from dib_tap_table_bytes as before)          */
 
 /* error codes */
@@ -564,6 +564,35 @@ int dib_squint_warp_forward(const float *in_dev, float *out_dev, int N, int C, i
 int dib_squint_warp_backward(const float *grad_out_dev, float *grad_in_dev, int N, int C, int H, int W, int layout,
                              const unsigned short *mats_dev, const unsigned short *base_x_dev, const unsigned short *base_y_dev,
                              void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Detection overlays: the picture the reference's `evaluate` saves of every image it scores (engine.py:382-383 around
+ * utils.py:322-353, `overlay_boxes_torch`) -- the image as the detector saw it with the outline of every detection above 0.5 on
+ * it -- as ONE launch for up to 32 images: planar fp16 / fp32 in, tight interleaved 8-bit RGB out, outlines already drawn.
+ *   in_dev[i]:  3 x H[i] x W[i] planar, contiguous, DIB_F16 or DIB_F32;  out_dev[i]: H[i] x W[i] x 3 bytes, RGB interleaved, rows
+ *   tight (what PIL.Image.fromarray takes);  H[i] * W[i] <= 2^30.
+ *   boxes_dev: device array of dib_overlay_box; boxes box_offset[i] .. box_offset[i + 1] - 1 (HOST array of B + 1 ints, not
+ *   decreasing) belong to image i, in drawing order.  boxes_dev may be NULL when there is no box.  rgb = R | G << 8 | B << 16 of the
+ *   OUTPUT (the caller reproduces the reference's colour handling: detectinblur_amd/overlay.py).
+ * Pixel value: k = trunc(float(x) * 255.0f), saturated to 0..255, NaN -> 0.  For 0 <= x < 256 / 255 that is torchvision's ToPILImage
+ * on a float tensor (`pic.mul(255).byte()`, what utils.py:331 calls after `.float()`); outside that domain the reference WRAPS
+ * (x = 1.01 -> 257 -> 1; negative values through the int conversion) where this saturates (1.01 -> 255, -0.2 -> 0).
+ * Outline of a box, after xa = min(x0, x1), xb = max(x0, x1), ya, yb likewise (corners beyond +-2^30 are taken as +-2^30).  Pixel
+ * (x, y) is painted iff all of
+ *   xa - 1 <= x <= xb + 1 and ya - 1 <= y <= yb + 1;
+ *   NOT (xa + 2 <= x <= xb - 2 and ya + 2 <= y <= yb - 2)                 (the interior);
+ *   NOT (x in {xa - 1, xb + 1} and y in {ya - 1, yb + 1})                 (the four outermost corner pixels);
+ *   the pixel lies inside the image (boxes are clipped; a box entirely outside paints nothing).
+ * A degenerate box (xa == xb or ya == yb) follows the same rule.  Where outlines overlap, the LAST painting box in drawing order wins,
+ * as a sequence of cv2.rectangle calls leaves it.  This rule is a reading of OpenCV's rectangle(thickness = 2) -- a closed polyline of
+ * thick lines: every edge a filled quad one pixel either side of the line, every vertex a filled circle of radius 1, which OpenCV draws
+ * as a plus.  It is the SPECIFICATION here and is NOT PINNED against cv2 (cv2 is not a dependency of this project and was not
+ * available where this was written).
+ * No atomics, no allocation, no host synchronisation: capturable into a graph.  B <= 32 (DIB_EINVAL beyond: split the list).
+ * ------------------------------------------------------------------------------------- */
+typedef struct dib_overlay_box { int x0, y0, x1, y1; unsigned int rgb; } dib_overlay_box;
+int dib_overlay_rgb8(const void *const *in_dev, int dtype, const int *H, const int *W, int B, const dib_overlay_box *boxes_dev,
+                     const int *box_offset, unsigned char *const *out_dev, void *stream);
 
 #ifdef __cplusplus
 }
