@@ -466,6 +466,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     detections against the dataset's COCO ground truth (boxes replaced by the expanded ones under
     `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
     `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES.
+    `deblur_first` / `deblurer` (reference :319-322): after the blur, the corruptions and the box growth, the first image of the batch
+    is replaced by `deblurer.deblur_(image)` (models/deblur.py: DeepDeblur's MSResNet, fp32) when the pass blurs or is the vanilla one.
     `image_output_folder` (reference :382-383): when given, every evaluated image is written as `<folder>/img<count>.png` -- the first
     image of the batch as the detector gets it (after blur and corruptions), with the outline of every detection above 0.5
     (overlay.py); `count` is the loop's index.  With more than one rank the files go to `<folder>/rank<r>/` (the reference lets the
@@ -475,8 +477,10 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     from .coco_eval import CocoEvaluator
     from .coco_utils import get_coco_api_from_dataset
     acc_mode = acc_mode_constant(blur_acc_mode)
-    if deblur_first:
-        raise NotImplementedError("--deblur_first is outside the built path (SURVEY.md section 2)")
+    # reference :319: the stage runs in a blurring pass and in the vanilla pass, never in a pass that is neither
+    deblurring = bool(deblur_first) and (blurring_images or vanilla_eval)
+    if deblurring and deblurer is None:
+        raise ValueError("evaluate(deblur_first=True) needs a deblurer (models.deblur.Deblurer)")
     jpeg_compressor = None
     if add_jpeg_artifact:                                                # reference :248-254
         from .models.jpeg import DiffJPEG
@@ -560,6 +564,11 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                                                jpeg_compressor=jpeg_compressor, acc_mode=acc_mode, tables=tables)
             if expand_target_boxes and blurring_images:
                 targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
+            if deblurring:
+                # reference :319-322, the FIRST image only (batch size 1 in every driver).  On a GPU the image stays there: three HIP
+                # kernels and MIOpen's convolutions on the current stream, no synchronisation (models/deblur.py).  The result is
+                # fp32, as the reference hands it on: the estimator's batcher, the detector and the overlay all read this image.
+                images_GPU[0] = deblurer.deblur_(images_GPU[0])
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
             est = None
             if use_ensemble and blur_estimator is not None:                  # reference :354-366 (the routing itself: below)

@@ -8,7 +8,9 @@ TensorBoard under the reference's tags.  Random-initialised models stand in for 
 given (synthetic throughput runs).  The reference README's command lines parse unchanged.
 `--save_images` (this repo) writes the reference's detection overlays (reference engine.py:382-383) under `--image_output_dir`: one
 subfolder per pass -- `clean` for the vanilla pass, `P<param>_E<fraction>` for each sweep cell (the reference hands every pass the
-same folder, so its 15 cells overwrite one another's img<count>.png; and it always writes, where this needs the flag)."""
+same folder, so its 15 cells overwrite one another's img<count>.png; and it always writes, where this needs the flag).
+`--deblur_first --deblurer_model_location DIR` puts DeepDeblur's MSResNet in front of the detector in every pass (reference
+evaluate.py:240-243, engine.py:319-322; models/deblur.py): the image stays on the device from the blur to the detector."""
 import os
 import argparse
 
@@ -61,6 +63,10 @@ def main(args):
     from . import kernel_choices
     kernel_choices.use_shipped_kernel_choices()      # shipped MIOpen / TunableOp choices, private copy per process (kernel_choices.py)
     reject_out_of_scope(args)
+    if getattr(args, "deblur_first", False) and not getattr(args, "deblurer_model_location", None):
+        raise SystemExit("--deblur_first needs --deblurer_model_location: a DeepDeblur experiment directory (models/model-<N>.pt) or a "
+                         "checkpoint file; the reference's default is a path on its author's disk and nothing is downloaded "
+                         "(`python -m detectinblur_amd.models.deblur --write_random DIR` writes a random one)")
     mp_ctx = utils.loader_context() if args.workers > 0 else None      # before anything touches the GPU (see utils.loader_context)
     utils.init_distributed_mode(args)
     print(args)
@@ -103,6 +109,12 @@ def main(args):
     else:
         model = detector(args.resume or args.model_path, mode_one=getattr(args, "mode_one_norm", False))
 
+    deblurer = None
+    if getattr(args, "deblur_first", False):                            # reference evaluate.py:240-243
+        from .models.deblur import Deblurer
+        deblurer = Deblurer(args.deblurer_model_location, device=device)
+    deblur_kw = dict(deblur_first=bool(getattr(args, "deblur_first", False)), deblurer=deblurer)
+
     def loader_for(tf):
         ds, _ = get_coco(args.data_path, "val", tf, synthetic=synthetic, with_masks=getattr(args, "with_masks", False))
         sampler = torch.utils.data.distributed.DistributedSampler(ds) if args.distributed else torch.utils.data.SequentialSampler(ds)
@@ -118,7 +130,7 @@ def main(args):
     if args.vanilla_eval:                                               # reference evaluate.py:226-262
         ce = evaluate(model, loader_for(get_transform(False, blur=False)), device=device, vanilla_eval=True,
                       distributed_mode=args.distributed, use_custom_image_norm=args.use_custom_image_norm,
-                      early_stop=args.early_stop, image_output_folder=pictures("clean"), **ens_kw)
+                      early_stop=args.early_stop, image_output_folder=pictures("clean"), **deblur_kw, **ens_kw)
         log_coco_stats(writer, "Clean", ce, 0)
         if writer is not None:
             writer.close()
@@ -137,7 +149,7 @@ def main(args):
                            blurring_images=True, gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                            use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
                            add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode,
-                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **ens_kw)
+                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **deblur_kw, **ens_kw)
             results["P%dE%d" % (param_index, fraction_index - 1)] = out
             if utils.is_main_process():
                 log_coco_stats(writer, "P" + str(param_index), out, fraction_index)

@@ -7,8 +7,8 @@ One process per GPU, DistributedDataParallel over RCCL (backend "nccl" on ROCm),
 SGD(lr 0.04, momentum 0.9, wd 1e-4) + MultiStepLR, seeds rank*1337, per-epoch checkpoints
 {'model','optimizer','lr_scheduler','args','epoch'} and --resume / --start_from_weights
 (reference train.py:89-391), TensorBoard scalars under --tensorboard_path.  The reference's README command
-lines parse unchanged; flags of subsystems outside the built path (deblur-first, custom BN, real-blur
-datasets) are accepted and refused with a clear message only when set.
+lines parse unchanged; flags of subsystems outside the built path (custom BN, real-blur datasets) are accepted
+and refused with a clear message only when set.  `--deblur_first` is read by evaluate.py alone, as in the reference.
 """
 import argparse
 import datetime
@@ -61,8 +61,7 @@ def seed_everything(distributed):
 
 # Flags of subsystems SURVEY.md section 2 places outside the built path: they parse (the reference's command
 # lines are accepted unchanged) and raise only when actually set.
-_OUT_OF_SCOPE = {"deblur_first": "the deblur-first pipeline (DeepDeblur)",
-                 "unfrozen_batch_norm": "trainable batch-norm conversion",
+_OUT_OF_SCOPE = {"unfrozen_batch_norm": "trainable batch-norm conversion",
                  "blurred_dataset": "real-blur datasets (GOPRO / REDS)", "expand_synth_boxes": "real-blur datasets (GOPRO / REDS)"}
 
 
@@ -144,13 +143,14 @@ def add_shared_flags(p):
     p.add_argument("--add_jpeg_artefacts", action="store_true", help="Add jpeg compression artifacts.")
     p.add_argument("--warp_in_model", action="store_true", help="Warp and dewarp images before and after backbone.")
     p.add_argument("--use_custom_image_norm", action="store_true", help="Use blur specific normalization on input to network.")
-    # outside the built path: accepted, refused when set (reject_out_of_scope)
-    p.add_argument("--deblur_first", action="store_true", help="(not built) deblur before detecting")
-    p.add_argument("--deblurer_model_location", default=None, help="(not built)")
+    p.add_argument("--deblur_first", action="store_true", help="Deblur with DeepDeblur (MSResNet) before detecting (evaluate.py only).")
+    p.add_argument("--deblurer_model_location", default=None, help="DeepDeblur experiment directory (models/model-<N>.pt) or a checkpoint "
+                   "file; no default (the reference's is a path on its author's disk) and nothing is downloaded")
     p.add_argument("--non_pos_aug_mix", action="store_true", help="Non positional augmix (training only; pixels on the GPU unless --cpu_blur).")
     p.add_argument("--include_pos_aug_mix", action="store_true", help="Include positional augmentations in augmix (with --non_pos_aug_mix).")
     p.add_argument("--aug_mix_target_expand", action="store_true",
                    help="Expand target boxes for AugMix according to positional shifts from spatial augmentations.")
+    # outside the built path: accepted, refused when set (reject_out_of_scope)
     p.add_argument("--unfrozen_batch_norm", action="store_true", help="(not built)")
     p.add_argument("--amp", action="store_true", help="(this repo) bfloat16 activations and matrix math "
                    "in the ResNet-50 body, the FPN and the RPN head's 3x3 convolution; fp32 master weights, gradients, optimizer, heads, losses")
@@ -206,6 +206,8 @@ def main(args):
     from . import kernel_choices
     kernel_choices.use_shipped_kernel_choices()      # shipped MIOpen / TunableOp choices, private copy per process (kernel_choices.py)
     reject_out_of_scope(args)
+    if getattr(args, "deblur_first", False):                            # reference train.py:467 parses the flag and never reads it
+        print("--deblur_first: only evaluate.py reads this flag; training and its evaluation passes run without the deblurrer")
     mp_ctx = utils.loader_context() if args.workers > 0 else None      # before anything touches the GPU (see utils.loader_context)
     utils.init_distributed_mode(args)
     print(args)

@@ -594,6 +594,37 @@ typedef struct dib_overlay_box { int x0, y0, x1, y1; unsigned int rgb; } dib_ove
 int dib_overlay_rgb8(const void *const *in_dev, int dtype, const int *H, const int *W, int B, const dib_overlay_box *boxes_dev,
                      const int *box_offset, unsigned char *const *out_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The deblur-first stage (reference engine.py:319-322, models/deblur/deblurInterface.py:42-63, `evaluate.py --deblur_first`):
+ * everything around MSResNet's convolutions, on the device.  The convolutions themselves are MIOpen's, each followed by
+ * dib_bias_act_nhwc.  n = n_scales, d = 2^(n - 1), Hp / Wp = H / W rounded up to multiples of d.
+ *
+ * dib_deblur_pyramid: in_dev planar [3][H][W] Half or fp32 in [0, 1] -> levels_dev[s] (HOST array of n device pointers), level s a
+ *   channels-last fp32 [Hp >> s][Wp >> s][6] tensor whose channels 0..2 are written (3..5: dib_deblur_shuffle_concat), the coarsest
+ *   level [..][3].  n launches.
+ *     quantise  q = trunc(x * 255), the product rounded in the image's own dtype first (Half 0.50195312 -> 128), clamped to 0..255,
+ *               NaN -> 0.  The reference's uint8 conversion of a value outside 0..255 is undefined; the clamp is this library's choice.
+ *     pad       bottom and right, mode "edge".
+ *     level s   level s - 1 smoothed per channel by a separable 7-tap Gaussian (sigma 2/3, weights exp(-x^2 / (2 sigma^2)) normalised in
+ *               float64, rounded to fp32), down the columns first, then along the rows, boundary "reflect" (d c b a | a b c d, periodic
+ *               when the halo is longer than the image); then the mean of each 2 x 2 block.  Products are accumulated from the first
+ *               tap to the last, the block as 0.25 * ((a + b) + (c + d)).  This is a READING of scikit-image's
+ *               pyramid_gaussian(img, n - 1, multichannel=True) on float32 (scipy.ndimage.gaussian_filter, then an order-1 resize
+ *               without anti-aliasing at a factor of exactly 2); scikit-image was not available where this was written: NOT PINNED.
+ *     store     every level minus 127.5 (MSResNet's mean shift).
+ * dib_deblur_shuffle_concat: in_dev [h][w][12] (conv_end's convolution WITHOUT bias), out_dev [2h][2w][6]:
+ *     out[2y + i][2x + j][3 + c] = in[y][x][4c + 2i + j] + bias[4c + 2i + j]          (bias + PixelShuffle(2) + cat, bit for bit)
+ * dib_deblur_finish: in_dev [Hp][Wp][3] (the finest level's last convolution WITHOUT bias) -> out_dev planar fp32 [3][H][W]:
+ *     out[c][y][x] = clamp(((in[y][x][c] + bias[c]) + 127.5) + 0.5, 0, 255) * (1.f / 255.f)    every step rounded in fp32, a NaN stays
+ *     a NaN: bit for bit torch's `(conv + 127.5)[:H, :W].add_(0.5).clamp_(0, 255) / 255` ON A GPU, where the reference runs it (ATen
+ *     divides a CUDA tensor by a scalar as a multiplication by the fp32 reciprocal; its CPU kernel divides: at most 1 ulp apart).
+ * Padded images of more than 2^30 pixels, n outside 1..4, H or W < 1, null or misaligned pointers (levels, in_dev and out_dev of
+ * shuffle_concat: 16 bytes): DIB_EINVAL, nothing launched.  No allocation, no host synchronisation: capturable into a graph.
+ * ------------------------------------------------------------------------------------- */
+int dib_deblur_pyramid(const void *in_dev, int dtype, int H, int W, int n_scales, float *const *levels_dev, void *stream);
+int dib_deblur_shuffle_concat(const float *in_dev, const float *bias_dev, float *out_dev, int h, int w, void *stream);
+int dib_deblur_finish(const float *in_dev, const float *bias_dev, float *out_dev, int H, int W, int Hp, int Wp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
