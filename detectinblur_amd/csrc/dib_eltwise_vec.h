@@ -4,14 +4,15 @@
 // the fp32 arithmetic in its order, and rounds ONCE (to nearest even) at the store, so each kernel is checkable bit for bit
 // against the torch expression evaluated in fp32 and cast once (tests/test_detector_ops.py, tests/test_amp_gpu.py).  Pure
 // streaming, HBM-bound; no atomics, no scratch.  dib_eltwise.hip instantiates the fp32 entry points, dib_eltwise_bf16.hip the
-// bf16 ones.
+// bf16 ones.  dib_eltwise_f16.hip instantiates ONE member, the bias epilogue, at 8 Half per lane for the deblurrer's Half graph
+// (models/deblur.py), whose ops round one by one: F16Lane::mid is that intermediate rounding.
 #pragma once
 #include "dib_common.h"
 #include <initializer_list>
 
 namespace dib {
 
-// ---- the two lane vectors: what the kernels below do not share ---------------------------------------------------------------
+// ---- the lane vectors: what the kernels below do not share ------------------------------------------------------------------
 // N elements in a Raw; Quad = 4 pooled channels of the stem pool, whose convolution side is fp32 in both forms.
 struct F32Lane {
   static constexpr int N = 4;
@@ -21,6 +22,7 @@ struct F32Lane {
   static __device__ __forceinline__ void unpack(const Raw u, float v[N]) { v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; }
   static __device__ __forceinline__ Raw pack(const float v[N]) { return make_float4(v[0], v[1], v[2], v[3]); }
   static __device__ __forceinline__ float relu(float v) { return relu_keep_nan(v); }
+  static __device__ __forceinline__ float mid(float v) { return v; }      // bias_act_kernel: nothing is rounded between its ops
   // bit k = element k > 0
   static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
     return (u.x > 0.f ? 1 : 0) | (u.y > 0.f ? 2 : 0) | (u.z > 0.f ? 4 : 0) | (u.w > 0.f ? 8 : 0);
@@ -57,6 +59,7 @@ struct Bf16Lane {
     return make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
   }
   static __device__ __forceinline__ float relu(float v) { return relu_keep_nan(v); }
+  static __device__ __forceinline__ float mid(float v) { return v; }
   // bit k = STORED element k > 0 (the value AFTER rounding: a positive fp32 below half of bf16's smallest denormal is stored
   // as zero and gets no gradient, as in the plain graph on the stored tensor)
   static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
@@ -74,6 +77,37 @@ struct Bf16Lane {
   }
   static __device__ __forceinline__ Quad pack_quad(const float4 m) { return make_uint2(pack2(m.x, m.y), pack2(m.z, m.w)); }
   static __device__ __forceinline__ float quad(const Quad q, int k) { return (k & 1) ? hi(k < 2 ? q.x : q.y) : lo(k < 2 ? q.x : q.y); }
+};
+
+// IEEE Half (the deblurrer under `--deblur_precision half`): 8 per 16-byte vector, converted with the round-to-nearest-even
+// conversions (v_cvt_f16_f32 / v_cvt_f32_f16; NaN stays NaN, what exceeds 65504 after rounding becomes +-inf, denormals are kept).
+// Only what bias_act_kernel reads is here: the other members of the family have no Half form.
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+
+struct F16Lane {
+  static constexpr int N = 8;
+  typedef uint4 Raw;
+  static __device__ __forceinline__ void unpack(const Raw u, float v[N]) {
+    const f32x8_t f = __builtin_convertvector(__builtin_bit_cast(f16x8_t, u), f32x8_t);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = f[k];
+  }
+  static __device__ __forceinline__ Raw pack(const float v[N]) {
+    const f32x8_t f = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    return __builtin_bit_cast(uint4, __builtin_convertvector(f, f16x8_t));
+  }
+  static __device__ __forceinline__ float relu(float v) { return relu_keep_nan(v); }
+  // torch's Half graph rounds `y + bias` before the residual is added (ResBlock: res = body(x); res += x)
+  static __device__ __forceinline__ float mid(float v) { return (float)(_Float16)v; }
+  static __device__ __forceinline__ unsigned sign_mask(const Raw u) {
+    float v[N];
+    unpack(u, v);
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) m |= (v[k] > 0.f ? 1u : 0u) << k;
+    return m;
+  }
 };
 
 template <class L>
@@ -109,6 +143,8 @@ __global__ __launch_bounds__(256) void bias_act_kernel(typename L::Raw *__restri
     if (RES) {
       float r[L::N];
       L::unpack(res[i], r);
+#pragma unroll
+      for (int k = 0; k < L::N; ++k) v[k] = L::mid(v[k]);
       add<L>(v, r);
     }
     if (RELU) {

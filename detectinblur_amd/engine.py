@@ -467,7 +467,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
     `blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES.
     `deblur_first` / `deblurer` (reference :319-322): after the blur, the corruptions and the box growth, the first image of the batch
-    is replaced by `deblurer.deblur_(image)` (models/deblur.py: DeepDeblur's MSResNet, fp32) when the pass blurs or is the vanilla one.
+    is replaced by `deblurer.deblur_(image)` (models/deblur.py: DeepDeblur's MSResNet, fp32, or Half when the deblurrer was built so)
+    when the pass blurs or is the vanilla one.
     `image_output_folder` (reference :382-383): when given, every evaluated image is written as `<folder>/img<count>.png` -- the first
     image of the batch as the detector gets it (after blur and corruptions), with the outline of every detection above 0.5
     (overlay.py); `count` is the loop's index.  With more than one rank the files go to `<folder>/rank<r>/` (the reference lets the
@@ -567,7 +568,8 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             if deblurring:
                 # reference :319-322, the FIRST image only (batch size 1 in every driver).  On a GPU the image stays there: three HIP
                 # kernels and MIOpen's convolutions on the current stream, no synchronisation (models/deblur.py).  The result is
-                # fp32, as the reference hands it on: the estimator's batcher, the detector and the overlay all read this image.
+                # fp32 (a Half deblurrer's: Half), as the reference hands it on: the estimator's batcher, the detector and the
+                # overlay all read this image, and all of them take either type (Half is what the blur hands them anyway).
                 images_GPU[0] = deblurer.deblur_(images_GPU[0])
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
             est = None

@@ -10,7 +10,9 @@ given (synthetic throughput runs).  The reference README's command lines parse u
 subfolder per pass -- `clean` for the vanilla pass, `P<param>_E<fraction>` for each sweep cell (the reference hands every pass the
 same folder, so its 15 cells overwrite one another's img<count>.png; and it always writes, where this needs the flag).
 `--deblur_first --deblurer_model_location DIR` puts DeepDeblur's MSResNet in front of the detector in every pass (reference
-evaluate.py:240-243, engine.py:319-322; models/deblur.py): the image stays on the device from the blur to the detector."""
+evaluate.py:240-243, engine.py:319-322; models/deblur.py): the image stays on the device from the blur to the detector.
+`--deblur_precision half` runs that stage as DeepDeblur's `--precision half` does (the module and its pyramid in Half) and hands the
+detector a Half image; `--amp` is independent of it and leaves the deblurrer alone."""
 import os
 import argparse
 
@@ -57,6 +59,14 @@ def _load(model, path):
         print("Loading from " + path)
         model.load_state_dict(torch.load(path, map_location="cpu", weights_only=False)["model"])
     return model
+
+
+def build_deblurer(args, device):
+    """reference evaluate.py:240-243: the Deblurer of `--deblur_first` in `--deblur_precision` (never `--amp`'s business), or None"""
+    if not getattr(args, "deblur_first", False):
+        return None
+    from .models.deblur import Deblurer
+    return Deblurer(args.deblurer_model_location, device=device, precision=getattr(args, "deblur_precision", "single"))
 
 
 def main(args):
@@ -109,10 +119,7 @@ def main(args):
     else:
         model = detector(args.resume or args.model_path, mode_one=getattr(args, "mode_one_norm", False))
 
-    deblurer = None
-    if getattr(args, "deblur_first", False):                            # reference evaluate.py:240-243
-        from .models.deblur import Deblurer
-        deblurer = Deblurer(args.deblurer_model_location, device=device)
+    deblurer = build_deblurer(args, device)
     deblur_kw = dict(deblur_first=bool(getattr(args, "deblur_first", False)), deblurer=deblurer)
 
     def loader_for(tf):

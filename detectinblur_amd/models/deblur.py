@@ -1,6 +1,6 @@
 """The deblur-first stage: DeepDeblur's multi-scale ResNet in front of the detector (reference engine.py:319-322,
 models/deblur/{deblurInterface,MSResNet,ResNet,common,model}.py; `evaluate.py --deblur_first --deblurer_model_location DIR`), the
-paper's "deblur, then detect" baseline.  Evaluation only, fp32 only (`--amp` leaves it fp32).
+paper's "deblur, then detect" baseline.  Evaluation only; fp32 unless `--deblur_precision half` (below); `--amp` does not touch it.
 
 What the reference computes on `images_GPU[0]` (blurred, corrupted, still [0, 1]), quirks included:
 
@@ -29,6 +29,19 @@ Two ways to the same values, as models/batchnorm.py has them:
     (coarser levels: after a bias-only pass, since the biased output also feeds conv_end) or into the finish kernel.  Nothing is
     concatenated, nothing synchronises, everything runs on the current stream.
   * torch: everything else (CPU, other shapes), steps 1-5 op for op.  It is what the HIP path is tested against.
+
+`precision="half"` (`--deblur_precision half`) is DeepDeblur's `--precision half` (reference models/deblur/deblurInterface.py:37,40,
+52-53): the checkpoint is loaded in fp32, strictly, and the module is then cast to Half; steps 1-3 stay fp32 (the reference builds the
+pyramid on the host) and every level is cast to Half; from there every op is a Half op, rounded once, to nearest even:
+
+  4. network   half(half(L) - 127.5); every convolution with its Half bias; ReLU; `res += x` (half(half(conv + b) + x): two roundings);
+               PixelShuffle and cat move values; plus 127.5 in Half.  No clamp: beyond 65504 a Half is inf, as in the reference.
+  5. finish    the crop, .add_(0.5), .clamp_(0, 255), / 255, each rounded to Half (on a GPU the last is one fp32 product, rounded once).
+               The Half [3, H, W] result replaces `images_GPU[0]`, and `deblurImage` returns a Half tensor.
+
+The HIP path then runs the Half forms of the same kernels (dib_deblur_*_f16, dib_bias_act_f16_nhwc behind MIOpen's Half convolutions
+without bias; n_feats % 8 == 0), the torch path the same module on `.half()` tensors.  Measured against a float64 run of the stage
+(scale 0..1): Half 7.8e-4, fp32 3.6e-7; bf16 would be 3e-3 to 5e-3, a grey level of 255, and is not built.
 
 `last_path` records which of the two ran last ("hip" / "torch"); FUSE_DEBLUR = False forces the torch path on the GPU for A/B runs.
 No pretrained DeepDeblur weights ship with this project and nothing is ever downloaded: `write_random_checkpoint` (or
@@ -162,48 +175,62 @@ def pyramid(q, n_scales):
 
 
 def finish(output, H, W):
-    """step 5: the network's [1, 3, Hp, Wp] level 0 -> [3, H, W] in [0, 1]"""
+    """step 5: the network's [1, 3, Hp, Wp] level 0 -> [3, H, W] in [0, 1], in the output's dtype (Half: every op rounds to Half)"""
     return (output[0, :, :H, :W].clone().add_(0.5).clamp_(0, 255) / 255)
 
 
 # ---- the same steps as HIP launches (csrc/dib_deblur.hip) -----------------------------------------------------------------------
 
-def pyramid_device(image, n_scales, levels=None):
+def pyramid_device(image, n_scales, levels=None, dtype=torch.float32):
     """steps 1-3 and the mean shift: a CUDA [3, H, W] Half / fp32 image -> the network's inputs, finest first: channels-last fp32
     [1, 6, Hp >> s, Wp >> s] tensors whose channels 0..2 hold level s minus 127.5 (3..5 are shuffle_concat_device's), the coarsest
-    [1, 3, ...].  n_scales launches on the current stream.  `levels`: tensors to write into (tests)."""
+    [1, 3, ...].  n_scales launches on the current stream.  `levels`: tensors to write into (tests).
+    dtype torch.float16: Half levels holding half(half(level) - 127.5), the pyramid itself computed in fp32 as above (the fp32 copies
+    of the levels in between live in a workspace allocated here)."""
     from .. import _lib
     image = image.contiguous()
     H, W = int(image.shape[1]), int(image.shape[2])
     d = 1 << (n_scales - 1)
     Hp, Wp = -(-H // d) * d, -(-W // d) * d
     if levels is None:
-        levels = [torch.empty((1, 6 if s < n_scales - 1 else 3, Hp >> s, Wp >> s), dtype=torch.float32, device=image.device,
+        levels = [torch.empty((1, 6 if s < n_scales - 1 else 3, Hp >> s, Wp >> s), dtype=dtype, device=image.device,
                               memory_format=torch.channels_last) for s in range(n_scales)]
-    _lib.check(_lib.lib().dib_deblur_pyramid(image.data_ptr(), _lib.DIB_F16 if image.dtype == torch.float16 else _lib.DIB_F32, H, W, n_scales,
+    in_dtype = _lib.DIB_F16 if image.dtype == torch.float16 else _lib.DIB_F32
+    if levels[0].dtype == torch.float16:
+        work = torch.empty(sum(3 * (Hp >> s) * (Wp >> s) for s in range(1, n_scales - 1)), dtype=torch.float32, device=image.device)
+        _lib.check(_lib.lib().dib_deblur_pyramid_f16(image.data_ptr(), in_dtype, H, W, n_scales, _lib.ptr_array([t.data_ptr() for t in levels]),
+                                                     work.data_ptr() if work.numel() else None, _lib.stream_of(image)))
+        return levels
+    _lib.check(_lib.lib().dib_deblur_pyramid(image.data_ptr(), in_dtype, H, W, n_scales,
                                              _lib.ptr_array([t.data_ptr() for t in levels]), _lib.stream_of(image)))
     return levels
 
 
 def shuffle_concat_device(raw, bias, level):
     """conv_end's raw output [1, 12, h, w] (channels-last, no bias) + bias, PixelShuffle(2), into channels 3..5 of `level`
-    [1, 6, 2h, 2w] (channels-last), in place of the reference's torch.cat.  Returns `level`."""
+    [1, 6, 2h, 2w] (channels-last), in place of the reference's torch.cat.  Returns `level`.  Both fp32, or both Half (the sum rounded
+    to Half; `bias` stays an fp32 vector, of Half values)."""
     from .. import _lib
     h, w = int(raw.shape[2]), int(raw.shape[3])
     assert tuple(raw.shape) == (1, 12, h, w) and tuple(level.shape) == (1, 6, 2 * h, 2 * w)
     assert raw.is_contiguous(memory_format=torch.channels_last) and level.is_contiguous(memory_format=torch.channels_last)
-    _lib.check(_lib.lib().dib_deblur_shuffle_concat(raw.data_ptr(), bias.data_ptr(), level.data_ptr(), h, w, _lib.stream_of(raw)))
+    assert raw.dtype == level.dtype and bias.dtype == torch.float32
+    l = _lib.lib()
+    fn = l.dib_deblur_shuffle_concat_f16 if raw.dtype == torch.float16 else l.dib_deblur_shuffle_concat
+    _lib.check(fn(raw.data_ptr(), bias.data_ptr(), level.data_ptr(), h, w, _lib.stream_of(raw)))
     return level
 
 
 def finish_device(raw, bias, H, W):
     """step 5 on the finest level's last convolution [1, 3, Hp, Wp] (channels-last, no bias): + bias, + 127.5, + 0.5, clamp, / 255,
-    cropped -> planar fp32 [3, H, W]"""
+    cropped -> planar [3, H, W] of `raw`'s dtype (Half: every one of those ops rounded to Half)"""
     from .. import _lib
     assert raw.shape[0] == 1 and raw.shape[1] == 3 and raw.is_contiguous(memory_format=torch.channels_last)
-    out = torch.empty((3, H, W), dtype=torch.float32, device=raw.device)
-    _lib.check(_lib.lib().dib_deblur_finish(raw.data_ptr(), bias.data_ptr(), out.data_ptr(), H, W, int(raw.shape[2]), int(raw.shape[3]),
-                                            _lib.stream_of(raw)))
+    assert bias.dtype == torch.float32
+    out = torch.empty((3, H, W), dtype=raw.dtype, device=raw.device)
+    l = _lib.lib()
+    fn = l.dib_deblur_finish_f16 if raw.dtype == torch.float16 else l.dib_deblur_finish
+    _lib.check(fn(raw.data_ptr(), bias.data_ptr(), out.data_ptr(), H, W, int(raw.shape[2]), int(raw.shape[3]), _lib.stream_of(raw)))
     return out
 
 
@@ -226,9 +253,16 @@ def find_checkpoint(model_location):
     return os.path.join(save_dir, "model-%d.pt" % epoch)
 
 
+PRECISIONS = ("single", "half")            # DeepDeblur's --precision
+
+
 class Deblurer(nn.Module):
-    def __init__(self, model_location, device=None):
+    def __init__(self, model_location, device=None, precision="single"):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError("Deblurer(precision=%r): one of %s" % (precision, ", ".join(repr(p) for p in PRECISIONS)))
+        self.precision = precision
+        self.dtype = torch.float16 if precision == "half" else torch.float32
         self.checkpoint = find_checkpoint(str(model_location))
         print("Loading model from {}".format(self.checkpoint))
         state = torch.load(self.checkpoint, map_location="cpu", weights_only=True)
@@ -237,6 +271,12 @@ class Deblurer(nn.Module):
         self.model.to(self.device)
         if self.device.type == "cuda":
             self.model.to(memory_format=torch.channels_last)
+        self._bias32 = {}
+        if precision == "half":                                            # reference deblurInterface.py:40, after the fp32 load
+            self.model.to(dtype=torch.float16)
+            if self.device.type == "cuda":
+                # the epilogue kernels read per-channel vectors as fp32: the Half biases, upcast (exact)
+                self._bias32 = {m: m.bias.detach().float() for m in self.model.modules() if isinstance(m, nn.Conv2d)}
         self.eval()
         for p in self.parameters():
             p.requires_grad_(False)
@@ -249,19 +289,21 @@ class Deblurer(nn.Module):
     # ---- which path ------------------------------------------------------------------------------------------------------------
     def _hip_ok(self, image):
         return (FUSE_DEBLUR and image.is_cuda and image.dim() == 3 and image.shape[0] == 3 and image.numel() > 0
-                and image.dtype in (torch.float16, torch.float32) and self.model.n_feats % 4 == 0 and 1 <= self.n_scales <= 4
+                and image.dtype in (torch.float16, torch.float32) and self.model.n_feats % (8 if self.precision == "half" else 4) == 0
+                and 1 <= self.n_scales <= 4
                 and next(self.model.parameters()).device == image.device)
 
     # ---- the torch path --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def _network_torch(self, q, H, W):
-        """q: fp32 [3, H, W] integers 0..255 -> the network's level 0, cropped: [1, 3, H, W] in 0..255"""
+        """q: fp32 [3, H, W] integers 0..255 -> the network's level 0, cropped: [1, 3, H, W] in 0..255, fp32 or (precision half) Half:
+        the fp32 pyramid cast to the module's dtype, as the reference's dataCommon.to does"""
         levels = pyramid(pad_to_multiple(q, 2 ** (self.n_scales - 1)), self.n_scales)
-        return self.model([l[None] for l in levels])[0][:, :, :H, :W]
+        return self.model([l[None].to(self.dtype) for l in levels])[0][:, :, :H, :W]
 
     @torch.no_grad()
     def deblurImage(self, image):
-        """The reference's method: an H x W x 3 uint8 array -> the [1, 3, H, W] fp32 tensor in 0..255 on the deblurrer's device,
+        """The reference's method: an H x W x 3 uint8 array -> the [1, 3, H, W] fp32 (precision half: Half) tensor in 0..255 on the deblurrer's device,
         BEFORE the finish step (the caller applies `.add_(0.5).clamp_(0, 255) / 255`).  Always the torch path."""
         q = torch.from_numpy(np.ascontiguousarray(np.asarray(image))).to(self.device).permute(2, 0, 1).float()
         self.last_path = "torch"
@@ -280,37 +322,40 @@ class Deblurer(nn.Module):
         from .. import _lib
         l, n = _lib.lib(), self.n_scales
         H, W = int(image.shape[1]), int(image.shape[2])
-        levels = pyramid_device(image, n)
+        half = self.precision == "half"
+        levels = pyramid_device(image, n, dtype=self.dtype)
         stream = _lib.stream_of(image)
+        epilogue = l.dib_bias_act_f16_nhwc if half else l.dib_bias_act_nhwc
+        bias_of = (lambda m: self._bias32[m]) if half else (lambda m: m.bias)
 
         def conv(x, m):
             y = F.conv2d(x, m.weight, None, 1, m.padding)
             return y.contiguous(memory_format=torch.channels_last)        # MIOpen's channels-last kernels give this layout already
 
         def bias_act(y, bias, residual=None, relu=False):
-            _lib.check(l.dib_bias_act_nhwc(y.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None, y.numel(),
-                                           y.shape[1], int(relu), stream))
+            _lib.check(epilogue(y.data_ptr(), bias.data_ptr(), residual.data_ptr() if residual is not None else None, y.numel(),
+                                y.shape[1], int(relu), stream))
             return y
 
         out, x = None, levels[n - 1]
         for s in range(n - 1, -1, -1):
             body = self.model.body_models[s].body
-            y = bias_act(conv(x, body[0]), body[0].bias)
+            y = bias_act(conv(x, body[0]), bias_of(body[0]))
             for block in list(body)[1:-1]:
-                t = bias_act(conv(y, block.body[0]), block.body[0].bias, relu=True)
-                y = bias_act(conv(t, block.body[2]), block.body[2].bias, residual=y)
+                t = bias_act(conv(y, block.body[0]), bias_of(block.body[0]), relu=True)
+                y = bias_act(conv(t, block.body[2]), bias_of(block.body[2]), residual=y)
             z = conv(y, body[-1])                                          # raw: its bias goes into the kernel that reads it
             if s > 0:
                 up = self.model.conv_end_models[s].uppath[0]
-                x = shuffle_concat_device(conv(bias_act(z, body[-1].bias), up), up.bias, levels[s - 1])
+                x = shuffle_concat_device(conv(bias_act(z, bias_of(body[-1])), up), bias_of(up), levels[s - 1])
             else:
-                out = finish_device(z, body[-1].bias, H, W)
+                out = finish_device(z, bias_of(body[-1]), H, W)
         self.last_path = "hip"
         return out
 
     # ---- entry point -----------------------------------------------------------------------------------------------------------
     def deblur_(self, image):
-        """[3, H, W] Half or fp32 in [0, 1] -> fp32 [3, H, W] in [0, 1] on the same device: steps 1-5."""
+        """[3, H, W] Half or fp32 in [0, 1] -> fp32 (precision half: Half) [3, H, W] in [0, 1] on the same device: steps 1-5."""
         if image.dim() != 3 or image.shape[0] != 3:
             raise ValueError("deblur_ expects a [3, H, W] image, got {}".format(tuple(image.shape)))
         if self._hip_ok(image):

@@ -8,7 +8,8 @@ SGD(lr 0.04, momentum 0.9, wd 1e-4) + MultiStepLR, seeds rank*1337, per-epoch ch
 {'model','optimizer','lr_scheduler','args','epoch'} and --resume / --start_from_weights
 (reference train.py:89-391), TensorBoard scalars under --tensorboard_path.  The reference's README command
 lines parse unchanged; flags of subsystems outside the built path (custom BN, real-blur datasets) are accepted
-and refused with a clear message only when set.  `--deblur_first` is read by evaluate.py alone, as in the reference.
+and refused with a clear message only when set.  `--deblur_first` (and its `--deblur_precision`) is read by evaluate.py alone, as in
+the reference.
 """
 import argparse
 import datetime
@@ -90,11 +91,23 @@ def reject_idle_blur_acc_mode(args):
                          "add --gpu_blur or drop --blur_acc_mode" % mode)
 
 
+DEBLUR_PRECISIONS = ("single", "half")      # models.deblur.PRECISIONS (kept apart: parsers load no library code)
+
+
+def reject_idle_deblur_precision(args):
+    """The deblurrer's precision without the deblurrer is refused at start, not silently ignored."""
+    precision = getattr(args, "deblur_precision", "single")
+    if precision != "single" and not getattr(args, "deblur_first", False):
+        raise SystemExit("--deblur_precision %s without --deblur_first: the flag is the arithmetic of the deblur-first stage and would do "
+                         "nothing; add --deblur_first (with --deblurer_model_location) or drop --deblur_precision" % precision)
+
+
 def reject_out_of_scope(args):
     for name, what in _OUT_OF_SCOPE.items():
         if getattr(args, name, False):
             raise SystemExit("--%s: %s is outside the built hot path (SURVEY.md section 2)" % (name, what))
     reject_idle_blur_acc_mode(args)
+    reject_idle_deblur_precision(args)
     if getattr(args, "amp", False) and getattr(args, "mode_one_norm", False):
         raise SystemExit("--amp with --mode_one_norm: the test-time batch-norm kernel (dib_bn_mode_one_nhwc) and its tolerances are fp32; "
                          "drop one of the two flags")
@@ -146,6 +159,10 @@ def add_shared_flags(p):
     p.add_argument("--deblur_first", action="store_true", help="Deblur with DeepDeblur (MSResNet) before detecting (evaluate.py only).")
     p.add_argument("--deblurer_model_location", default=None, help="DeepDeblur experiment directory (models/model-<N>.pt) or a checkpoint "
                    "file; no default (the reference's is a path on its author's disk) and nothing is downloaded")
+    p.add_argument("--deblur_precision", default="single", choices=DEBLUR_PRECISIONS,
+                   help="(this repo's name for DeepDeblur's --precision) arithmetic of the --deblur_first stage (evaluate.py only). single: fp32 "
+                        "(default). half: the module and its input pyramid cast to Half, every op rounded to Half, a Half image handed on; "
+                        "independent of --amp, which never touches the deblurrer.")
     p.add_argument("--non_pos_aug_mix", action="store_true", help="Non positional augmix (training only; pixels on the GPU unless --cpu_blur).")
     p.add_argument("--include_pos_aug_mix", action="store_true", help="Include positional augmentations in augmix (with --non_pos_aug_mix).")
     p.add_argument("--aug_mix_target_expand", action="store_true",
@@ -208,6 +225,8 @@ def main(args):
     reject_out_of_scope(args)
     if getattr(args, "deblur_first", False):                            # reference train.py:467 parses the flag and never reads it
         print("--deblur_first: only evaluate.py reads this flag; training and its evaluation passes run without the deblurrer")
+    if getattr(args, "deblur_precision", "single") != "single":
+        print("--deblur_precision: only evaluate.py reads this flag, like the stage it belongs to")
     mp_ctx = utils.loader_context() if args.workers > 0 else None      # before anything touches the GPU (see utils.loader_context)
     utils.init_distributed_mode(args)
     print(args)

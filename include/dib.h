@@ -445,6 +445,19 @@ int dib_stem_pool_forward_bf16(const float *x_dev, const float *bias_dev, void *
 int dib_stem_pool_backward_bf16(const void *grad_out_dev, const unsigned short *arg_dev, float *grad_in_dev, int N, int H, int W, int C,
                                 void *stream);
 
+/* The IEEE Half form of dib_bias_act_nhwc, the only Half member of the family: the epilogue behind every convolution of the deblurrer
+ * under `evaluate.py --deblur_first --deblur_precision half` (below).  x_dev and residual_dev are channels-last Half (raw 16-bit words),
+ * bias_dev an fp32 vector holding Half values (the reference's Half biases, upcast).  It reproduces torch's Half ops in their order,
+ * each computed on the upcast values and rounded once to nearest even:
+ *     bias only        x = half(x + b)
+ *     bias + ReLU      x = relu(half(x + b))            a NaN stays a NaN, everything else that is not > 0 becomes +0
+ *     bias + residual  x = half(half(x + b) + r)        TWO roundings: the reference's ResBlock is `res = body(x); res += x` on Half
+ *                                                       tensors (with relu != 0: the ReLU of that)
+ * A sum beyond 65504 becomes +-inf as torch's does; Half denormals are kept.  8 elements per lane where C % 8 == 0 and the tensors
+ * are 16-byte aligned; one per lane otherwise, as dib_bias_act_nhwc (the deblurrer's coarser scales end in 3 channels).  n_elems not
+ * a multiple of C, null pointers, tensors not aligned to their elements: DIB_EINVAL, nothing launched. */
+int dib_bias_act_f16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C, int relu, void *stream);
+
 /* Frozen batch-norm folds of n trunk convolutions in one launch per 32 (torchvision's FrozenBatchNorm2d behind every ResNet
  * convolution, reference models/faster_rcnn.py:367; training re-folds every step because the weights move):
  *   scale = bn_w * rsqrt(var + eps);  shift = bn_b - mean * scale;  wf[co][...] = w[co][...] * scale[co]
@@ -624,6 +637,29 @@ int dib_overlay_rgb8(const void *const *in_dev, int dtype, const int *H, const i
 int dib_deblur_pyramid(const void *in_dev, int dtype, int H, int W, int n_scales, float *const *levels_dev, void *stream);
 int dib_deblur_shuffle_concat(const float *in_dev, const float *bias_dev, float *out_dev, int h, int w, void *stream);
 int dib_deblur_finish(const float *in_dev, const float *bias_dev, float *out_dev, int H, int W, int Hp, int Wp, void *stream);
+
+/* The same three steps for DeepDeblur's `--precision half` (reference models/deblur/deblurInterface.py:37,40,52-53: the model and the
+ * pyramid are cast to Half, so every op of the network runs and rounds in Half; `evaluate.py --deblur_precision half`).  Levels,
+ * convolution outputs and the image are IEEE Half (raw 16-bit words), biases fp32 vectors holding Half values; "half()" rounds to
+ * nearest even; the convolutions are MIOpen's on Half tensors, each followed by dib_bias_act_f16_nhwc.  The same kernels as above,
+ * templated over the stored type: same argument checks (DIB_EINVAL, nothing launched), same limits, capturable.
+ *
+ * dib_deblur_pyramid_f16: in_dev as above (Half or fp32 image) -> levels_dev[s], channels-last Half [Hp >> s][Wp >> s][6] (coarsest:
+ *   [..][3]), 16-byte aligned, channels 0..2 written.  Quantise, pad and every level L_s are computed exactly as dib_deblur_pyramid
+ *   computes them, in fp32 (the reference builds the pyramid on the host before it casts); stored is half(half(L_s) - 127.5): the
+ *   upload's cast, then MSResNet's Half `x - 127.5`.  Level 0 holds integers and is exact.  A coarser level is filtered from the fp32
+ *   values of the one above, not from its rounded ones: work_dev (16-byte aligned) receives fp32 [Hp >> s][Wp >> s][3] for
+ *   s = 1 .. n - 2, back to back -- 0 bytes for n <= 2 (work_dev may be NULL), 3 Hp Wp bytes for n = 3, 3.75 Hp Wp for n = 4.
+ * dib_deblur_shuffle_concat_f16: in_dev Half [h][w][12], out_dev Half [2h][2w][6], both 16-byte aligned:
+ *     out[2y + i][2x + j][3 + c] = half(in[y][x][4c + 2i + j] + bias[4c + 2i + j])    bit for bit torch's Half bias add + PixelShuffle + cat
+ * dib_deblur_finish_f16: in_dev Half [Hp][Wp][3] -> out_dev planar Half [3][H][W] (2-byte aligned; 8-byte vectors where they are):
+ *     out[c][y][x] = half(clamp(half(half(half(in + bias) + 127.5) + 0.5), 0, 255) * (1.f / 255.f))
+ *     every op of `(conv + 127.5)[:H, :W].add_(0.5).clamp_(0, 255) / 255` rounded to Half; the last product is formed in fp32 and
+ *     rounded once, as ATen does for a Half tensor on a GPU.  A NaN stays a NaN.  No clamp anywhere else: a Half activation beyond
+ *     65504 is inf and travels on as torch's would. */
+int dib_deblur_pyramid_f16(const void *in_dev, int dtype, int H, int W, int n_scales, void *const *levels_dev, float *work_dev, void *stream);
+int dib_deblur_shuffle_concat_f16(const void *in_dev, const float *bias_dev, void *out_dev, int h, int w, void *stream);
+int dib_deblur_finish_f16(const void *in_dev, const float *bias_dev, void *out_dev, int H, int W, int Hp, int Wp, void *stream);
 
 #ifdef __cplusplus
 }
