@@ -5,20 +5,62 @@
 // Detectron / Mask R-CNN definition of RoIAlign with aligned=False (no half-pixel shift, RoI
 // width/height clamped to >= 1) so that results match a plain-PyTorch fp32 restatement
 // (tests/test_detector_ops.py).
+//
+// The arithmetic of the five RoIAlign kernels is stated once each: roi_geom() (a RoI's origin, bin size, sampling grid),
+// sample_coord() (where sample i of bin p lies) and axis_tap() (the Detectron rule for one axis: axis_outside()'s test, the clamp,
+// the two cells and their weights).  The kernels differ in their work split and in how they accumulate, not in these.  The library is
+// built with -ffp-contract=off and tests/test_roi_nms_reference.py pins every kernel bit for bit at the rule's
+// discontinuities: the order of the fp32 operations in the three helpers is part of the contract.
 #include "dib_common.h"
 
 namespace dib {
 
-// bilinear sample of one H x W plane at (y, x); out-of-range samples contribute 0 (Detectron rule)
-__device__ inline float bilinear(const float *__restrict__ p, int H, int W, float y, float x) {
-  if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return 0.f;
-  y = fmaxf(y, 0.f);
-  x = fmaxf(x, 0.f);
-  int y0 = (int)y, x0 = (int)x, y1, x1;
-  if (y0 >= H - 1) { y0 = y1 = H - 1; y = (float)y0; } else y1 = y0 + 1;
-  if (x0 >= W - 1) { x0 = x1 = W - 1; x = (float)x0; } else x1 = x0 + 1;
-  const float ly = y - y0, lx = x - x0, hy = 1.f - ly, hx = 1.f - lx;
-  return hy * hx * p[y0 * W + x0] + hy * lx * p[y0 * W + x1] + ly * hx * p[y1 * W + x0] + ly * lx * p[y1 * W + x1];
+struct RoiGeom { float x1, y1, bw, bh; int gh, gw, b; float cnt; };
+
+// r = (batch index, x1, y1, x2, y2) in image coordinates; sr <= 0: adaptive grid, ceil(bin size) samples per bin side
+__device__ __forceinline__ RoiGeom roi_geom(const float *r, float scale, int P, int sr, int aligned) {
+  RoiGeom g;
+  g.b = (int)r[0];
+  const float off = aligned ? 0.5f : 0.f;
+  g.x1 = r[1] * scale - off; g.y1 = r[2] * scale - off;
+  const float x2 = r[3] * scale - off, y2 = r[4] * scale - off;
+  float rw = x2 - g.x1, rh = y2 - g.y1;
+  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
+  g.bh = rh / P; g.bw = rw / P;
+  g.gh = sr > 0 ? sr : (int)ceilf(rh / P); g.gw = sr > 0 ? sr : (int)ceilf(rw / P);
+  g.cnt = (float)max(g.gh * g.gw, 1);
+  return g;
+}
+
+// coordinate of sample i (of `grid`) in bin p along one axis
+__device__ __forceinline__ float sample_coord(float origin, int p, float bin, int i, int grid) {
+  return origin + p * bin + (i + 0.5f) * bin / grid;
+}
+
+// One axis of the bilinear rule (Detectron): a coordinate outside [-1, n] contributes nothing (a NaN counts as inside and
+// lands on cell 0 through fmaxf); inside, it is clamped at 0, and from the last cell on both cells are n - 1 and the
+// coordinate snaps to it (l = 0, h = 1; `last` says so: i1 == i0).  Cell i0 weighs h, cell i1 weighs l.  ok == !axis_outside().
+__device__ __forceinline__ bool axis_outside(float v, int n) { return v < -1.0f || v > (float)n; }
+
+struct AxisTap { bool ok, last; int i0, i1; float l, h; };
+
+__device__ __forceinline__ AxisTap axis_tap(float v, int n) {
+  AxisTap a;
+  a.ok = !axis_outside(v, n);
+  v = fmaxf(v, 0.f);
+  a.i0 = (int)v;
+  a.last = a.i0 >= n - 1;
+  if (a.last) { a.i0 = a.i1 = n - 1; v = (float)a.i0; } else a.i1 = a.i0 + 1;
+  a.l = v - a.i0; a.h = 1.f - a.l;
+  return a;
+}
+
+// bilinear sample of one H x W plane at (y, x); out-of-range samples contribute 0 without touching memory
+__device__ __forceinline__ float bilinear(const float *__restrict__ p, int H, int W, float y, float x) {
+  const AxisTap ay = axis_tap(y, H), ax = axis_tap(x, W);
+  if (!(ay.ok && ax.ok)) return 0.f;
+  return ay.h * ax.h * p[ay.i0 * W + ax.i0] + ay.h * ax.l * p[ay.i0 * W + ax.i1] + ay.l * ax.h * p[ay.i1 * W + ax.i0] +
+         ay.l * ax.l * p[ay.i1 * W + ax.i1];
 }
 
 // one thread per output element; consecutive threads walk pw, ph, c of one RoI: neighbouring
@@ -30,25 +72,14 @@ __global__ void roi_align_fwd_kernel(const float *__restrict__ feat, const float
   if (idx >= total) return;
   const int pw = (int)(idx % P), ph = (int)((idx / P) % P), c = (int)((idx / ((long long)P * P)) % C);
   const int k = (int)(idx / ((long long)P * P * C));
-  const float *r = rois + (size_t)k * 5;
-  const int b = (int)r[0];
-  const float off = aligned ? 0.5f : 0.f;
-  const float x1 = r[1] * scale - off, y1 = r[2] * scale - off, x2 = r[3] * scale - off, y2 = r[4] * scale - off;
-  float rw = x2 - x1, rh = y2 - y1;
-  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
-  const float bh = rh / P, bw = rw / P;
-  const int gh = sr > 0 ? sr : (int)ceilf(rh / P), gw = sr > 0 ? sr : (int)ceilf(rw / P);
-  const float cnt = (float)max(gh * gw, 1);
-  const float *plane = feat + ((size_t)b * C + c) * H * W;
+  const RoiGeom g = roi_geom(rois + (size_t)k * 5, scale, P, sr, aligned);
+  const float *plane = feat + ((size_t)g.b * C + c) * H * W;
   float acc = 0.f;
-  for (int iy = 0; iy < gh; ++iy) {
-    const float y = y1 + ph * bh + (iy + 0.5f) * bh / gh;
-    for (int ix = 0; ix < gw; ++ix) {
-      const float x = x1 + pw * bw + (ix + 0.5f) * bw / gw;
-      acc += bilinear(plane, H, W, y, x);
-    }
+  for (int iy = 0; iy < g.gh; ++iy) {
+    const float y = sample_coord(g.y1, ph, g.bh, iy, g.gh);
+    for (int ix = 0; ix < g.gw; ++ix) acc += bilinear(plane, H, W, y, sample_coord(g.x1, pw, g.bw, ix, g.gw));
   }
-  out[idx] = acc / cnt;
+  out[idx] = acc / g.cnt;
 }
 
 __global__ void roi_align_bwd_kernel(const float *__restrict__ gout, const float *__restrict__ rois, int K, int C, int H,
@@ -58,30 +89,18 @@ __global__ void roi_align_bwd_kernel(const float *__restrict__ gout, const float
   if (idx >= total) return;
   const int pw = (int)(idx % P), ph = (int)((idx / P) % P), c = (int)((idx / ((long long)P * P)) % C);
   const int k = (int)(idx / ((long long)P * P * C));
-  const float *r = rois + (size_t)k * 5;
-  const int b = (int)r[0];
-  const float off = aligned ? 0.5f : 0.f;
-  const float x1 = r[1] * scale - off, y1 = r[2] * scale - off, x2 = r[3] * scale - off, y2 = r[4] * scale - off;
-  float rw = x2 - x1, rh = y2 - y1;
-  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
-  const float bh = rh / P, bw = rw / P;
-  const int gh = sr > 0 ? sr : (int)ceilf(rh / P), gw = sr > 0 ? sr : (int)ceilf(rw / P);
-  const float g = gout[idx] / (float)max(gh * gw, 1);
-  float *plane = gfeat + ((size_t)b * C + c) * H * W;
-  for (int iy = 0; iy < gh; ++iy) {
-    float y = y1 + ph * bh + (iy + 0.5f) * bh / gh;
-    for (int ix = 0; ix < gw; ++ix) {
-      float x = x1 + pw * bw + (ix + 0.5f) * bw / gw;
-      if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) continue;
-      float yy = fmaxf(y, 0.f), xx = fmaxf(x, 0.f);
-      int y0 = (int)yy, x0 = (int)xx, y1i, x1i;
-      if (y0 >= H - 1) { y0 = y1i = H - 1; yy = (float)y0; } else y1i = y0 + 1;
-      if (x0 >= W - 1) { x0 = x1i = W - 1; xx = (float)x0; } else x1i = x0 + 1;
-      const float ly = yy - y0, lx = xx - x0, hy = 1.f - ly, hx = 1.f - lx;
-      atomicAdd(plane + y0 * W + x0, g * hy * hx);
-      atomicAdd(plane + y0 * W + x1i, g * hy * lx);
-      atomicAdd(plane + y1i * W + x0, g * ly * hx);
-      atomicAdd(plane + y1i * W + x1i, g * ly * lx);
+  const RoiGeom g = roi_geom(rois + (size_t)k * 5, scale, P, sr, aligned);
+  const float gv = gout[idx] / g.cnt;
+  float *plane = gfeat + ((size_t)g.b * C + c) * H * W;
+  for (int iy = 0; iy < g.gh; ++iy) {
+    const AxisTap ay = axis_tap(sample_coord(g.y1, ph, g.bh, iy, g.gh), H);
+    for (int ix = 0; ix < g.gw; ++ix) {
+      const AxisTap ax = axis_tap(sample_coord(g.x1, pw, g.bw, ix, g.gw), W);
+      if (!(ay.ok && ax.ok)) continue;
+      atomicAdd(plane + ay.i0 * W + ax.i0, gv * ay.h * ax.h);
+      atomicAdd(plane + ay.i0 * W + ax.i1, gv * ay.h * ax.l);
+      atomicAdd(plane + ay.i1 * W + ax.i0, gv * ay.l * ax.h);
+      atomicAdd(plane + ay.i1 * W + ax.i1, gv * ay.l * ax.l);
     }
   }
 }
@@ -106,22 +125,6 @@ struct RoiLevels {
 };
 constexpr int ROI_CCHUNK = 256;
 
-struct RoiGeom { float x1, y1, bw, bh; int gh, gw, b; float cnt; };
-
-__device__ inline RoiGeom roi_geom(const float *r, float scale, int P, int sr, int aligned) {
-  RoiGeom g;
-  g.b = (int)r[0];
-  const float off = aligned ? 0.5f : 0.f;
-  g.x1 = r[1] * scale - off; g.y1 = r[2] * scale - off;
-  const float x2 = r[3] * scale - off, y2 = r[4] * scale - off;
-  float rw = x2 - g.x1, rh = y2 - g.y1;
-  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
-  g.bh = rh / P; g.bw = rw / P;
-  g.gh = sr > 0 ? sr : (int)ceilf(rh / P); g.gw = sr > 0 ? sr : (int)ceilf(rw / P);
-  g.cnt = (float)max(g.gh * g.gw, 1);
-  return g;
-}
-
 __global__ __launch_bounds__(256) void roi_align_fwd_nhwc_kernel(RoiLevels L, const float *__restrict__ rois,
                                                                  const int *__restrict__ level, int C, int P, int sr,
                                                                  int aligned, float *__restrict__ out) {
@@ -138,19 +141,13 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc_kernel(RoiLevels L, co
     for (int c = lane; c < nc; c += 64) {
       float acc = 0.f;
       for (int iy = 0; iy < g.gh; ++iy) {
-        const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / g.gh;
+        const AxisTap ay = axis_tap(sample_coord(g.y1, ph, g.bh, iy, g.gh), H);
         for (int ix = 0; ix < g.gw; ++ix) {
-          const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / g.gw;
+          const AxisTap ax = axis_tap(sample_coord(g.x1, pw, g.bw, ix, g.gw), W);
           float v = 0.f;
-          if (!(y < -1.0f || y > (float)H || x < -1.0f || x > (float)W)) {
-            float yy = fmaxf(y, 0.f), xx = fmaxf(x, 0.f);
-            int y0 = (int)yy, x0 = (int)xx, y1i, x1i;
-            if (y0 >= H - 1) { y0 = y1i = H - 1; yy = (float)y0; } else y1i = y0 + 1;
-            if (x0 >= W - 1) { x0 = x1i = W - 1; xx = (float)x0; } else x1i = x0 + 1;
-            const float ly = yy - y0, lx = xx - x0, hy = 1.f - ly, hx = 1.f - lx;
-            v = hy * hx * base[((size_t)y0 * W + x0) * C + c] + hy * lx * base[((size_t)y0 * W + x1i) * C + c] +
-                ly * hx * base[((size_t)y1i * W + x0) * C + c] + ly * lx * base[((size_t)y1i * W + x1i) * C + c];
-          }
+          if (ay.ok && ax.ok)
+            v = ay.h * ax.h * base[((size_t)ay.i0 * W + ax.i0) * C + c] + ay.h * ax.l * base[((size_t)ay.i0 * W + ax.i1) * C + c] +
+                ay.l * ax.h * base[((size_t)ay.i1 * W + ax.i0) * C + c] + ay.l * ax.l * base[((size_t)ay.i1 * W + ax.i1) * C + c];
           acc += v;
         }
       }
@@ -183,25 +180,11 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc_sr_kernel(RoiLevels L,
     for (int bin = wave; bin < PP; bin += 4) {
       const int ph = bin / P, pw = bin - ph * P;
       float4 v[SR * SR][4];
-      float wy[SR][2], wx[SR][2];
-      bool oky[SR], okx[SR];
-      int ys[SR][2], xs[SR][2];
+      AxisTap ay[SR], ax[SR];
 #pragma unroll
       for (int i = 0; i < SR; ++i) {
-        const float y = g.y1 + ph * g.bh + (i + 0.5f) * g.bh / g.gh;
-        oky[i] = !(y < -1.0f || y > (float)H);
-        float yy = fmaxf(y, 0.f);
-        int y0 = (int)yy, y1i;
-        if (y0 >= H - 1) { y0 = y1i = H - 1; yy = (float)y0; } else y1i = y0 + 1;
-        ys[i][0] = y0; ys[i][1] = y1i;
-        wy[i][1] = yy - y0; wy[i][0] = 1.f - wy[i][1];
-        const float x = g.x1 + pw * g.bw + (i + 0.5f) * g.bw / g.gw;
-        okx[i] = !(x < -1.0f || x > (float)W);
-        float xx = fmaxf(x, 0.f);
-        int x0 = (int)xx, x1i;
-        if (x0 >= W - 1) { x0 = x1i = W - 1; xx = (float)x0; } else x1i = x0 + 1;
-        xs[i][0] = x0; xs[i][1] = x1i;
-        wx[i][1] = xx - x0; wx[i][0] = 1.f - wx[i][1];
+        ay[i] = axis_tap(sample_coord(g.y1, ph, g.bh, i, g.gh), H);
+        ax[i] = axis_tap(sample_coord(g.x1, pw, g.bw, i, g.gw), W);
       }
 #pragma unroll
       for (int iy = 0; iy < SR; ++iy)
@@ -209,15 +192,16 @@ __global__ __launch_bounds__(256) void roi_align_fwd_nhwc_sr_kernel(RoiLevels L,
         for (int ix = 0; ix < SR; ++ix)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            v[iy * SR + ix][q] = *reinterpret_cast<const float4 *>(base + ((size_t)ys[iy][q >> 1] * W + xs[ix][q & 1]) * C + c);
+            v[iy * SR + ix][q] = *reinterpret_cast<const float4 *>(
+                base + ((size_t)(q >> 1 ? ay[iy].i1 : ay[iy].i0) * W + (q & 1 ? ax[ix].i1 : ax[ix].i0)) * C + c);
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int iy = 0; iy < SR; ++iy)
 #pragma unroll
         for (int ix = 0; ix < SR; ++ix) {
           const float4 *q = v[iy * SR + ix];
-          const float hy = wy[iy][0], ly = wy[iy][1], hx = wx[ix][0], lx = wx[ix][1];
-          const bool ok = oky[iy] && okx[ix];
+          const float hy = ay[iy].h, ly = ay[iy].l, hx = ax[ix].h, lx = ax[ix].l;
+          const bool ok = ay[iy].ok && ax[ix].ok;
           acc.x += ok ? hy * hx * q[0].x + hy * lx * q[1].x + ly * hx * q[2].x + ly * lx * q[3].x : 0.f;
           acc.y += ok ? hy * hx * q[0].y + hy * lx * q[1].y + ly * hx * q[2].y + ly * lx * q[3].y : 0.f;
           acc.z += ok ? hy * hx * q[0].z + hy * lx * q[1].z + ly * hx * q[2].z + ly * lx * q[3].z : 0.f;
@@ -257,41 +241,34 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_kernel(RoiLevels L, co
   const int nrows = P * g.gh, ncols = P * g.gw;
   for (int row = wave; row < nrows; row += 4) {
     const int ph = row / g.gh, iy = row - ph * g.gh;
-    const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / g.gh;
-    if (y < -1.0f || y > (float)H) continue;
-    float yy = fmaxf(y, 0.f);
-    int y0 = (int)yy, y1i;
-    if (y0 >= H - 1) { y0 = y1i = H - 1; yy = (float)y0; } else y1i = y0 + 1;
-    const float ly = yy - y0, hy = 1.f - ly;
-    float *r0 = base + (size_t)y0 * W * C, *r1 = base + (size_t)y1i * W * C;
+    const float y = sample_coord(g.y1, ph, g.bh, iy, g.gh);
+    if (axis_outside(y, H)) continue;   // tested before the taps are formed, here and for x: nothing is computed for a sample that is dropped
+    const AxisTap ay = axis_tap(y, H);
+    float *r0 = base + (size_t)ay.i0 * W * C, *r1 = base + (size_t)ay.i1 * W * C;
     for (int c = lane; c < nc; c += 64) {
       const float *gt = tile + c * PP + ph * P;
       int cur = -2;                 // column whose sum hA holds; hB: column cur + 1
       float hA = 0.f, hB = 0.f;
       auto flush = [&](int col, float h) {
         if (col < 0 || col >= W) return;
-        atomicAdd(r0 + (size_t)col * C + c, hy * h);
-        if (ly != 0.f) atomicAdd(r1 + (size_t)col * C + c, ly * h);
+        atomicAdd(r0 + (size_t)col * C + c, ay.h * h);
+        if (ay.l != 0.f) atomicAdd(r1 + (size_t)col * C + c, ay.l * h);
       };
       for (int px = 0; px < ncols; ++px) {
         const int pw = px / g.gw, ix = px - pw * g.gw;
-        const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / g.gw;
-        if (x < -1.0f || x > (float)W) continue;
-        float xx = fmaxf(x, 0.f);
-        int x0 = (int)xx;
-        bool edge = false;
-        if (x0 >= W - 1) { x0 = W - 1; xx = (float)x0; edge = true; }
-        const float lx = xx - x0, hx = 1.f - lx;
-        if (x0 != cur) {            // wave-uniform: x does not depend on the lane
+        const float x = sample_coord(g.x1, pw, g.bw, ix, g.gw);
+        if (axis_outside(x, W)) continue;
+        const AxisTap ax = axis_tap(x, W);
+        if (ax.i0 != cur) {         // wave-uniform: x does not depend on the lane
           if (cur >= 0) flush(cur, hA);
-          if (x0 == cur + 1) hA = hB;
+          if (ax.i0 == cur + 1) hA = hB;
           else { if (cur >= 0) flush(cur + 1, hB); hA = 0.f; }
           hB = 0.f;
-          cur = x0;
+          cur = ax.i0;
         }
         const float gv = gt[pw] * inv_cnt;
-        hA += gv * hx;
-        if (!edge) hB += gv * lx;
+        hA += gv * ax.h;
+        if (!ax.last) hB += gv * ax.l;   // at the right edge there is no second column: nothing is added, not gv * 0
       }
       if (cur >= 0) { flush(cur, hA); flush(cur + 1, hB); }
     }
@@ -434,30 +411,33 @@ __global__ __launch_bounds__(1024) void nms_reduce_kernel(const unsigned long lo
 
 using namespace dib;
 
+// The two planar entry points: one thread per output element, `in_dev` -> `out_dev` is feat -> out or grad_out -> grad_feat.
+using RoiPlanarKernel = void (*)(const float *, const float *, int, int, int, int, float, int, int, int, float *);
+
+static int launch_planar(RoiPlanarKernel kernel, const char *who, const float *in_dev, const float *rois_dev, int K, int C, int H,
+                         int W, float spatial_scale, int pooled, int sampling_ratio, int aligned, float *out_dev, void *stream) {
+  if (K < 0 || C <= 0 || H <= 0 || W <= 0 || pooled <= 0) { set_error("%s: bad shape", who); return DIB_EINVAL; }
+  if (K == 0) return DIB_OK;
+  if (!in_dev || !rois_dev || !out_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
+  const long long total = (long long)K * C * pooled * pooled;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in_dev, rois_dev, K, C, H, W,
+                     spatial_scale, pooled, sampling_ratio, aligned, out_dev);
+  DIB_HIP_CHECK(hipGetLastError());
+  return DIB_OK;
+}
+
 extern "C" int dib_roi_align_forward(const float *feat_dev, const float *rois_dev, int K, int C, int H, int W,
                                      float spatial_scale, int pooled, int sampling_ratio, int aligned, float *out_dev,
                                      void *stream) {
-  if (K < 0 || C <= 0 || H <= 0 || W <= 0 || pooled <= 0) { set_error("dib_roi_align_forward: bad shape"); return DIB_EINVAL; }
-  if (K == 0) return DIB_OK;
-  if (!feat_dev || !rois_dev || !out_dev) { set_error("dib_roi_align_forward: null pointer"); return DIB_EINVAL; }
-  const long long total = (long long)K * C * pooled * pooled;
-  hipLaunchKernelGGL(roi_align_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, feat_dev,
-                     rois_dev, K, C, H, W, spatial_scale, pooled, sampling_ratio, aligned, out_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return launch_planar(roi_align_fwd_kernel, "dib_roi_align_forward", feat_dev, rois_dev, K, C, H, W, spatial_scale, pooled,
+                       sampling_ratio, aligned, out_dev, stream);
 }
 
 extern "C" int dib_roi_align_backward(const float *grad_out_dev, const float *rois_dev, int K, int C, int H, int W,
                                       float spatial_scale, int pooled, int sampling_ratio, int aligned,
                                       float *grad_feat_dev, void *stream) {
-  if (K < 0 || C <= 0 || H <= 0 || W <= 0 || pooled <= 0) { set_error("dib_roi_align_backward: bad shape"); return DIB_EINVAL; }
-  if (K == 0) return DIB_OK;
-  if (!grad_out_dev || !rois_dev || !grad_feat_dev) { set_error("dib_roi_align_backward: null pointer"); return DIB_EINVAL; }
-  const long long total = (long long)K * C * pooled * pooled;
-  hipLaunchKernelGGL(roi_align_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     grad_out_dev, rois_dev, K, C, H, W, spatial_scale, pooled, sampling_ratio, aligned, grad_feat_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return launch_planar(roi_align_bwd_kernel, "dib_roi_align_backward", grad_out_dev, rois_dev, K, C, H, W, spatial_scale, pooled,
+                       sampling_ratio, aligned, grad_feat_dev, stream);
 }
 
 static int fill_levels(RoiLevels &L, const void *const *ptrs, bool grads, const int *H, const int *W, const float *scale,
@@ -474,44 +454,48 @@ static int fill_levels(RoiLevels &L, const void *const *ptrs, bool grads, const 
   return DIB_OK;
 }
 
+// The two channels-last entry points: the checks, the level table, the grid (RoI, channel chunk) and the LDS tile's bytes;
+// `launch(L, grid, lds_bytes)` starts the kernel.  `io_dev` is the flat [K][C][P][P] side: out, or grad_out.
+template <class Launch>
+static int launch_nhwc(const char *who, const void *const *level_ptrs, bool grads, const int *H, const int *W, const float *scale,
+                       int n_levels, const float *rois_dev, const int *level_dev, int K, int C, int pooled, const float *io_dev,
+                       Launch launch) {
+  if (K < 0 || C <= 0 || pooled <= 0 || pooled > 7) { set_error("%s: bad shape (pooled <= 7)", who); return DIB_EINVAL; }
+  if (K == 0) return DIB_OK;
+  if (!rois_dev || !io_dev || (n_levels > 1 && !level_dev)) { set_error("%s: null pointer", who); return DIB_EINVAL; }
+  RoiLevels L;
+  int rc = fill_levels(L, level_ptrs, grads, H, W, scale, n_levels, who);
+  if (rc != DIB_OK) return rc;
+  const int nc = C < ROI_CCHUNK ? C : ROI_CCHUNK;
+  launch(L, dim3(K, (C + ROI_CCHUNK - 1) / ROI_CCHUNK), (size_t)nc * pooled * pooled * sizeof(float));
+  DIB_HIP_CHECK(hipGetLastError());
+  return DIB_OK;
+}
+
 extern "C" int dib_roi_align_nhwc_forward(const float *const *feat_dev, const int *H, const int *W, const float *scale,
                                           int n_levels, const float *rois_dev, const int *level_dev, int K, int C, int pooled,
                                           int sampling_ratio, int aligned, float *out_dev, void *stream) {
-  if (K < 0 || C <= 0 || pooled <= 0 || pooled > 7) { set_error("dib_roi_align_nhwc_forward: bad shape (pooled <= 7)"); return DIB_EINVAL; }
-  if (K == 0) return DIB_OK;
-  if (!rois_dev || !out_dev || (n_levels > 1 && !level_dev)) { set_error("dib_roi_align_nhwc_forward: null pointer"); return DIB_EINVAL; }
-  RoiLevels L;
-  int rc = fill_levels(L, (const void *const *)feat_dev, false, H, W, scale, n_levels, "dib_roi_align_nhwc_forward");
-  if (rc != DIB_OK) return rc;
-  const int nc = C < ROI_CCHUNK ? C : ROI_CCHUNK;
-  bool vec = sampling_ratio == 2 && (C % 4) == 0;
-  for (int i = 0; i < n_levels; ++i) vec = vec && (((uintptr_t)feat_dev[i]) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(roi_align_fwd_nhwc_sr_kernel<2>, dim3(K, (C + ROI_CCHUNK - 1) / ROI_CCHUNK), dim3(256),
-                       (size_t)nc * pooled * pooled * sizeof(float), (hipStream_t)stream, L, rois_dev, level_dev, C, pooled, aligned, out_dev);
-  else
-    hipLaunchKernelGGL(roi_align_fwd_nhwc_kernel, dim3(K, (C + ROI_CCHUNK - 1) / ROI_CCHUNK), dim3(256),
-                       (size_t)nc * pooled * pooled * sizeof(float), (hipStream_t)stream, L, rois_dev, level_dev, C, pooled,
-                       sampling_ratio, aligned, out_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return launch_nhwc("dib_roi_align_nhwc_forward", (const void *const *)feat_dev, false, H, W, scale, n_levels, rois_dev, level_dev,
+                     K, C, pooled, out_dev, [&](const RoiLevels &L, dim3 grid, size_t lds) {
+    bool vec = sampling_ratio == 2 && (C % 4) == 0;
+    for (int i = 0; i < n_levels; ++i) vec = vec && (((uintptr_t)feat_dev[i]) & 15) == 0;
+    if (vec)
+      hipLaunchKernelGGL(roi_align_fwd_nhwc_sr_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, L, rois_dev, level_dev, C,
+                         pooled, aligned, out_dev);
+    else
+      hipLaunchKernelGGL(roi_align_fwd_nhwc_kernel, grid, dim3(256), lds, (hipStream_t)stream, L, rois_dev, level_dev, C, pooled,
+                         sampling_ratio, aligned, out_dev);
+  });
 }
 
 extern "C" int dib_roi_align_nhwc_backward(const float *grad_out_dev, const int *H, const int *W, const float *scale,
                                            int n_levels, const float *rois_dev, const int *level_dev, int K, int C, int pooled,
                                            int sampling_ratio, int aligned, float *const *grad_feat_dev, void *stream) {
-  if (K < 0 || C <= 0 || pooled <= 0 || pooled > 7) { set_error("dib_roi_align_nhwc_backward: bad shape (pooled <= 7)"); return DIB_EINVAL; }
-  if (K == 0) return DIB_OK;
-  if (!rois_dev || !grad_out_dev || (n_levels > 1 && !level_dev)) { set_error("dib_roi_align_nhwc_backward: null pointer"); return DIB_EINVAL; }
-  RoiLevels L;
-  int rc = fill_levels(L, (const void *const *)grad_feat_dev, true, H, W, scale, n_levels, "dib_roi_align_nhwc_backward");
-  if (rc != DIB_OK) return rc;
-  const int nc = C < ROI_CCHUNK ? C : ROI_CCHUNK;
-  hipLaunchKernelGGL(roi_align_bwd_nhwc_kernel, dim3(K, (C + ROI_CCHUNK - 1) / ROI_CCHUNK), dim3(256),
-                     (size_t)nc * pooled * pooled * sizeof(float), (hipStream_t)stream, L, rois_dev, level_dev, C, pooled,
-                     sampling_ratio, aligned, grad_out_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return launch_nhwc("dib_roi_align_nhwc_backward", (const void *const *)grad_feat_dev, true, H, W, scale, n_levels, rois_dev,
+                     level_dev, K, C, pooled, grad_out_dev, [&](const RoiLevels &L, dim3 grid, size_t lds) {
+    hipLaunchKernelGGL(roi_align_bwd_nhwc_kernel, grid, dim3(256), lds, (hipStream_t)stream, L, rois_dev, level_dev, C, pooled,
+                       sampling_ratio, aligned, grad_out_dev);
+  });
 }
 
 extern "C" int dib_coco_box_iou(const double *dt_dev, const double *gt_dev, const unsigned char *iscrowd_dev, int m, int n,

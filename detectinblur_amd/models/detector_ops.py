@@ -519,6 +519,12 @@ def _is_nhwc(f):
             and f.is_contiguous(memory_format=torch.channels_last))
 
 
+def _level_arrays(shapes, scales):
+    """The H / W / scale arrays of dib_roi_align_nhwc_forward / _backward for levels of the given [N, C, H, W] shapes."""
+    return (_lib.int_array([sh[2] for sh in shapes]), _lib.int_array([sh[3] for sh in shapes]),
+            (ctypes.c_float * len(shapes))(*[float(s) for s in scales]))
+
+
 class _RoIAlignNHWC(torch.autograd.Function):
     """Channels-last RoIAlign over 1..4 pyramid levels in one launch (include/dib.h:
     dib_roi_align_nhwc_forward / _backward); `level` is a device int32 [K] tensor."""
@@ -527,8 +533,7 @@ class _RoIAlignNHWC(torch.autograd.Function):
     def forward(ctx, rois, level, scales, pooled, sampling_ratio, aligned, *feats):
         rois = rois.contiguous().float()
         K, C = rois.shape[0], feats[0].shape[1]
-        hs, ws = _lib.int_array([f.shape[2] for f in feats]), _lib.int_array([f.shape[3] for f in feats])
-        sc = (ctypes.c_float * len(feats))(*[float(s) for s in scales])
+        hs, ws, sc = _level_arrays([f.shape for f in feats], scales)
         out = torch.empty((K, C, pooled, pooled), dtype=torch.float32, device=rois.device)
         _lib.check(_lib.lib().dib_roi_align_nhwc_forward(
             _lib.ptr_array([f.data_ptr() for f in feats]), hs, ws, sc, len(feats), rois.data_ptr(),
@@ -546,8 +551,7 @@ class _RoIAlignNHWC(torch.autograd.Function):
         grads = [torch.empty(sh, dtype=torch.float32, device=grad_out.device, memory_format=torch.channels_last).zero_()
                  for sh in shapes]
         g = grad_out.contiguous().float()
-        hs, ws = _lib.int_array([sh[2] for sh in shapes]), _lib.int_array([sh[3] for sh in shapes])
-        sc = (ctypes.c_float * len(shapes))(*scales)
+        hs, ws, sc = _level_arrays(shapes, scales)
         _lib.check(_lib.lib().dib_roi_align_nhwc_backward(
             g.data_ptr(), hs, ws, sc, len(shapes), rois.data_ptr(), level.data_ptr() if level is not None else None,
             rois.shape[0], shapes[0][1], pooled, sr, aligned, _lib.ptr_array([x.data_ptr() for x in grads]),
@@ -594,14 +598,14 @@ class MultiScaleRoIAlign(torch.nn.Module):
         if len(feats) == 1:
             return roi_align(feats[0], rois, scales[0], P, self.sampling_ratio)
         k_min, k_max = -math.log2(scales[0]), -math.log2(scales[-1])
-        area = box_area(rois[:, 1:])
-        lvl = torch.floor(4 + torch.log2(torch.sqrt(area) / 224) + 1e-6).clamp(min=k_min, max=k_max).long() - int(k_min)
+        k = torch.floor(4 + torch.log2(torch.sqrt(box_area(rois[:, 1:])) / 224) + 1e-6)        # FPN eq. 1, before clamping
         if len(feats) <= 4 and P <= 7 and all(_is_nhwc(f) for f in feats):
             # channels-last pyramid: every level in one launch, no per-level index_select / scatter / host sync
             # nan_to_num + clamp: boxes of a diverged step (NaN / inf area) must still name a real level
-            lvl = torch.nan_to_num(torch.floor(4 + torch.log2(torch.sqrt(area) / 224) + 1e-6), nan=k_min, posinf=k_max, neginf=k_min)
+            lvl = torch.nan_to_num(k, nan=k_min, posinf=k_max, neginf=k_min)
             lvl = (lvl.clamp(min=k_min, max=k_max) - k_min).to(torch.int32)
             return _RoIAlignNHWC.apply(rois, lvl, scales, P, self.sampling_ratio, False, *feats)
+        lvl = k.clamp(min=k_min, max=k_max).long() - int(k_min)
         out = torch.zeros((rois.shape[0], feats[0].shape[1], P, P), dtype=feats[0].dtype, device=rois.device)
         for i, (f, s) in enumerate(zip(feats, scales)):
             idx = torch.where(lvl == i)[0]
