@@ -14,6 +14,11 @@
 //      in order), the 16 partial results merge in lane order; then the mix above and scale / shift.
 //   3. bn_apply_kernel: the in-place pass of bias_act_kernel (dib_eltwise_vec.h) with a scale.
 // Every reduction runs in an order fixed by the shape alone: two calls on the same input are bitwise equal.
+//
+// Acclimation (reference models/batchnorm.py:142-157, dib_bn_acclimate_nhwc) is the online form of the same remedy, in the same
+// three launches: bn_acclimate_finalize_kernel folds the batch's mean and UNBIASED variance into the running statistics with
+// factor a (the momentum, or 1 / num_batches_tracked after its bump), writes them back and normalises with the updated pair;
+// the bumped counter is stored by the apply launch (bn_apply_bump_kernel), behind every read of the old value.
 #include "dib_common.h"
 
 namespace dib {
@@ -119,16 +124,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const float4 *__
   }
 }
 
-__global__ __launch_bounds__(64 * BN_FIN_LANES) void bn_finalize_kernel(BnGeom g, const float *__restrict__ ws_mean, const float *__restrict__ ws_m2,
-                                                          const float *__restrict__ weight, const float *__restrict__ bias,
-                                                          const float *__restrict__ running_mean, const float *__restrict__ running_var,
-                                                          const long long *__restrict__ nbt_dev, long long nbt_host, float eps,
-                                                          float *__restrict__ scale, float *__restrict__ shift,
-                                                          float *__restrict__ stats) {
-  __shared__ float sh[3][BN_FIN_LANES][64];
+// The slices of one channel merged by BN_FIN_LANES lanes (lane j: slices j, j + 16, ..., in order), then the 16 partial results
+// in lane order.  Every lane of the workgroup calls this (it holds a barrier); true on the one lane per channel (j == 0) that
+// leaves with the channel's (count, mean, M2) in `acc`.  Both finalize kernels call it: the merge order is stated once.
+__device__ inline bool bn_merge_slices(const BnGeom &g, const float *__restrict__ ws_mean, const float *__restrict__ ws_m2,
+                                       float (*sh)[BN_FIN_LANES][64], int c, Welford &acc) {
   const int cl = threadIdx.x & 63, j = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  Welford acc = {0.f, 0.f, 0.f};
+  acc = {0.f, 0.f, 0.f};
   if (c < g.C) {
     // BN_FIN_BATCH slices' loads in flight, then their merges in slice order: the partial results were just written by workgroups
     // on other XCDs, and load round trips, not bandwidth, are this kernel's cost (7-15 us per layer: profiles/mode_one_norm.txt)
@@ -151,8 +153,21 @@ __global__ __launch_bounds__(64 * BN_FIN_LANES) void bn_finalize_kernel(BnGeom g
   sh[1][j][cl] = acc.mean;
   sh[2][j][cl] = acc.m2;
   __syncthreads();
-  if (j != 0 || c >= g.C) return;
+  if (j != 0 || c >= g.C) return false;
   for (int k = 1; k < BN_FIN_LANES; ++k) chan_merge(acc, Welford{sh[0][k][cl], sh[1][k][cl], sh[2][k][cl]});
+  return true;
+}
+
+__global__ __launch_bounds__(64 * BN_FIN_LANES) void bn_finalize_kernel(BnGeom g, const float *__restrict__ ws_mean, const float *__restrict__ ws_m2,
+                                                          const float *__restrict__ weight, const float *__restrict__ bias,
+                                                          const float *__restrict__ running_mean, const float *__restrict__ running_var,
+                                                          const long long *__restrict__ nbt_dev, long long nbt_host, float eps,
+                                                          float *__restrict__ scale, float *__restrict__ shift,
+                                                          float *__restrict__ stats) {
+  __shared__ float sh[3][BN_FIN_LANES][64];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  Welford acc;
+  if (!bn_merge_slices(g, ws_mean, ws_m2, sh, c, acc)) return;
   // the reference's factors: torch.true_divide of int64 tensors, i.e. float32(n) / float32(n + 1) and 1 / float32(n + 1)
   const long long nb = nbt_dev ? *nbt_dev : nbt_host;
   const float f = (float)nb / (float)(nb + 1);
@@ -170,10 +185,54 @@ __global__ __launch_bounds__(64 * BN_FIN_LANES) void bn_finalize_kernel(BnGeom g
   }
 }
 
+// Acclimation (reference models/batchnorm.py:142-157): the batch's statistics are folded into the running ones, which are written
+// back, and the layer normalises with the UPDATED running statistics.  One lane per channel reads and writes that channel's
+// running pair.  The counter is only READ here, by every workgroup: its bumped value is stored by the apply launch
+// (bn_apply_bump_kernel), which the stream orders behind all of these reads.
+__global__ __launch_bounds__(64 * BN_FIN_LANES) void bn_acclimate_finalize_kernel(BnGeom g, const float *__restrict__ ws_mean,
+                                                          const float *__restrict__ ws_m2, const float *__restrict__ weight,
+                                                          const float *__restrict__ bias, float *__restrict__ running_mean,
+                                                          float *__restrict__ running_var, const long long *__restrict__ nbt_dev,
+                                                          int bump, float momentum, float eps, float *__restrict__ scale,
+                                                          float *__restrict__ shift, float *__restrict__ stats) {
+  __shared__ float sh[3][BN_FIN_LANES][64];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  // the lane that will hold the channel's statistics asks for everything else it needs BEFORE the merge, so that these loads and
+  // the division travel under the merge's own load round trips instead of behind them (profiles/acclimate_norm.txt).
+  // a is the reference's exponential_average_factor (:110-122): the momentum, or 1 / float(num_batches_tracked) AFTER the bump (python
+  // floats: the division in double, rounded once to the float that ATen's fp32 update takes); without a bump and without a
+  // momentum it stays 0.0
+  float a = momentum, rm = 0.f, rv = 1.f, w = 1.f, b = 0.f;
+  if ((threadIdx.x >> 6) == 0 && c < g.C) {
+    if (momentum < 0.f) a = bump ? (float)(1.0 / (double)(*nbt_dev + 1)) : 0.f;
+    rm = running_mean[c];
+    rv = running_var[c];
+    if (weight) w = weight[c];
+    if (bias) b = bias[c];
+  }
+  Welford acc;
+  if (!bn_merge_slices(g, ws_mean, ws_m2, sh, c, acc)) return;
+  const float keep = 1.f - a;
+  const float var_u = acc.m2 / (acc.n - 1.f);      // unbiased: what training-mode batch_norm folds into running_var
+  const float km = keep * rm, am = a * acc.mean;
+  const float kv = keep * rv, av = a * var_u;
+  const float mean = km + am, var = kv + av;
+  running_mean[c] = mean;
+  running_var[c] = var;
+  const float sc = w * (1.f / sqrtf(var + eps));
+  scale[c] = sc;
+  shift[c] = b - mean * sc;
+  if (stats) {
+    stats[c] = acc.mean;
+    stats[g.C + c] = var_u;
+    stats[2 * g.C + c] = mean;
+    stats[3 * g.C + c] = var;
+  }
+}
+
 template <bool RES, bool RELU>
-__global__ __launch_bounds__(256) void bn_apply_kernel(float4 *__restrict__ x, const float4 *__restrict__ scale,
-                                                       const float4 *__restrict__ shift, const float4 *__restrict__ res, long long n4,
-                                                       int C4) {
+__device__ inline void bn_apply_body(float4 *__restrict__ x, const float4 *__restrict__ scale, const float4 *__restrict__ shift,
+                                     const float4 *__restrict__ res, long long n4, int C4) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     float4 v = x[i];
     const int c = (int)(i % C4);
@@ -183,6 +242,23 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(float4 *__restrict__ x, c
     if (RELU) { v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w); }
     x[i] = v;
   }
+}
+
+template <bool RES, bool RELU>
+__global__ __launch_bounds__(256) void bn_apply_kernel(float4 *__restrict__ x, const float4 *__restrict__ scale,
+                                                       const float4 *__restrict__ shift, const float4 *__restrict__ res, long long n4,
+                                                       int C4) {
+  bn_apply_body<RES, RELU>(x, scale, shift, res, n4, C4);
+}
+
+// the apply pass of an acclimating layer in training mode: one lane also stores num_batches_tracked + 1.  Nothing in this launch
+// reads the counter but that lane, and every reader of the old value (bn_acclimate_finalize_kernel) ran in the launch before.
+template <bool RES, bool RELU>
+__global__ __launch_bounds__(256) void bn_apply_bump_kernel(float4 *__restrict__ x, const float4 *__restrict__ scale,
+                                                            const float4 *__restrict__ shift, const float4 *__restrict__ res,
+                                                            long long n4, int C4, long long *__restrict__ nbt) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *nbt = *nbt + 1;
+  bn_apply_body<RES, RELU>(x, scale, shift, res, n4, C4);
 }
 
 // Grid of the partial statistics: up to 64 quads (256 channels) side by side, as many pixel rows as fill BN_THREADS lanes,
@@ -245,6 +321,49 @@ extern "C" int dib_bn_mode_one_nhwc(float *x_dev, const float *residual_dev, lon
 #define DIB_LAUNCH(RES, RELU)                                                                                                  \
   hipLaunchKernelGGL((bn_apply_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev, (const float4 *)scale, \
                      (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4)
+  if (residual_dev) { if (relu) DIB_LAUNCH(true, true); else DIB_LAUNCH(true, false); }
+  else { if (relu) DIB_LAUNCH(false, true); else DIB_LAUNCH(false, false); }
+#undef DIB_LAUNCH
+  DIB_HIP_CHECK(hipGetLastError());
+  return DIB_OK;
+}
+
+extern "C" int dib_bn_acclimate_nhwc(float *x_dev, const float *residual_dev, long long n_pix, int C, const float *weight_dev,
+                                     const float *bias_dev, float *running_mean_dev, float *running_var_dev, long long *num_batches_dev,
+                                     int bump, float momentum, float eps, int relu, void *workspace_dev, size_t workspace_bytes,
+                                     float *stats_dev, void *stream) {
+  if (n_pix <= 0 || C <= 0 || (C % 4) != 0 || C / 4 > 65535LL * 64) { set_error("dib_bn_acclimate_nhwc: needs n_pix > 0 and C %% 4 == 0 (C = %d)", C); return DIB_EINVAL; }
+  if (n_pix < 2) { set_error("dib_bn_acclimate_nhwc: more than one value per channel is needed to fold an unbiased variance in"); return DIB_EINVAL; }
+  if (!x_dev || !running_mean_dev || !running_var_dev || !workspace_dev) { set_error("dib_bn_acclimate_nhwc: null pointer"); return DIB_EINVAL; }
+  if (bump && !num_batches_dev) { set_error("dib_bn_acclimate_nhwc: bump without num_batches_dev"); return DIB_EINVAL; }
+  if (!(momentum <= 1.f)) { set_error("dib_bn_acclimate_nhwc: momentum above 1 (negative: cumulative average)"); return DIB_EINVAL; }
+  if ((((uintptr_t)x_dev | (uintptr_t)residual_dev | (uintptr_t)workspace_dev) & 15) != 0 || ((uintptr_t)num_batches_dev & 7) != 0) {
+    set_error("dib_bn_acclimate_nhwc: x, residual and workspace must be 16-byte aligned, num_batches_dev 8-byte aligned");
+    return DIB_EINVAL;
+  }
+  const BnGeom g = bn_geometry(n_pix, C);
+  const size_t need = bn_workspace_floats(g) * sizeof(float);
+  if (workspace_bytes < need) { set_error("dib_bn_acclimate_nhwc: workspace of %zu bytes, needs %zu", workspace_bytes, need); return DIB_EINVAL; }
+  float *ws = (float *)workspace_dev;
+  float *scale = ws, *shift = ws + C, *ws_mean = ws + 2 * (size_t)C, *ws_m2 = ws_mean + (size_t)g.S * C;
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned chunks = (unsigned)((g.Q + g.QB - 1) / g.QB);
+  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)g.S, chunks), dim3(BN_THREADS), 0, s, (const float4 *)x_dev, g, ws_mean, ws_m2);
+  hipLaunchKernelGGL(bn_acclimate_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64 * BN_FIN_LANES), 0, s, g, ws_mean, ws_m2,
+                     weight_dev, bias_dev, running_mean_dev, running_var_dev, (const long long *)num_batches_dev, bump ? 1 : 0, momentum, eps,
+                     scale, shift, stats_dev);
+  const long long n4 = n_pix * (C / 4);
+  long long blocks = (n4 + 255) / 256;
+  if (blocks > 0x7fffffffLL) blocks = 0x7fffffffLL;
+#define DIB_LAUNCH(RES, RELU)                                                                                                       \
+  do {                                                                                                                              \
+    if (bump)                                                                                                                       \
+      hipLaunchKernelGGL((bn_apply_bump_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev,               \
+                         (const float4 *)scale, (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4, num_batches_dev);   \
+    else                                                                                                                            \
+      hipLaunchKernelGGL((bn_apply_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev,                    \
+                         (const float4 *)scale, (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4);                    \
+  } while (0)
   if (residual_dev) { if (relu) DIB_LAUNCH(true, true); else DIB_LAUNCH(true, false); }
   else { if (relu) DIB_LAUNCH(false, true); else DIB_LAUNCH(false, false); }
 #undef DIB_LAUNCH

@@ -469,6 +469,10 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     `deblur_first` / `deblurer` (reference :319-322): after the blur, the corruptions and the box growth, the first image of the batch
     is replaced by `deblurer.deblur_(image)` (models/deblur.py: DeepDeblur's MSResNet, fp32, or Half when the deblurrer was built so)
     when the pass blurs or is the vanilla one.
+    A model that evaluate.py marked for online batch-norm statistics (`acclimate_norm`, with `acclimation_carry_over`): after eval() its
+    batch-norm layers go back into training mode (utils.turn_batch_norm_on) and, unless the statistics carry over, the pass starts
+    from the snapshot (utils.restore_BN_stats_from_old, in place).  The graphed trunk and the pipelined loop carry the state: the
+    kernels write it through the buffers' addresses, and image i's trunk is queued on the same stream before image i + 1's.
     `image_output_folder` (reference :382-383): when given, every evaluated image is written as `<folder>/img<count>.png` -- the first
     image of the batch as the detector gets it (after blur and corruptions), with the outline of every detection above 0.5
     (overlay.py); `count` is the loop's index.  With more than one rank the files go to `<folder>/rank<r>/` (the reference lets the
@@ -503,6 +507,18 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             blur_estimator.eval()
     else:
         model.eval()
+        core = getattr(model, "module", model)
+        if getattr(core, "acclimate_norm", False):
+            # --acclimate_norm (evaluate.py): eval() has just put the batch-norm layers back into eval mode; online statistics need
+            # them in training mode (the counter's bump, the cumulative average).  Every pass starts from the snapshot unless the
+            # statistics are to run on through the passes: copies in place on this stream, no synchronisation.  Whether the state can
+            # live on the device is decided here, once: if not, the layers rebind their buffers on the torch path and nothing of
+            # this model is captured.
+            utils.turn_batch_norm_on(core)
+            if not getattr(core, "acclimation_carry_over", False):
+                utils.restore_BN_stats_from_old(core)
+            if graphed and not utils.acclimation_on_device(core, device):
+                core.graph_inference = graphed = False
     metric_logger = utils.MetricLogger(delimiter="  ")
     coco = get_coco_api_from_dataset(data_loader.dataset)                # reference :271-273
     coco_evaluator = CocoEvaluator(coco, ["bbox"], device=device if device.type == "cuda" else None)

@@ -12,7 +12,9 @@ same folder, so its 15 cells overwrite one another's img<count>.png; and it alwa
 `--deblur_first --deblurer_model_location DIR` puts DeepDeblur's MSResNet in front of the detector in every pass (reference
 evaluate.py:240-243, engine.py:319-322; models/deblur.py): the image stays on the device from the blur to the detector.
 `--deblur_precision half` runs that stage as DeepDeblur's `--precision half` does (the module and its pyramid in Half) and hands the
-detector a Half image; `--amp` is independent of it and leaves the deblurrer alone."""
+detector a Half image; `--amp` is independent of it and leaves the deblurrer alone.
+`--acclimate_norm` (this repo's flag for the reference layer's `acclimation_mode`, models/batchnorm.py:142-157, and the helpers of
+its utils.py:80-217): online batch-norm statistics, updated on the device image by image (models/batchnorm.py, engine.evaluate)."""
 import os
 import argparse
 
@@ -29,6 +31,7 @@ from .train import _seed_worker, add_shared_flags, detector_size_kwargs, get_tra
 
 SWEEP_PARAMS = [0.005, 0.001, 0.00005]
 SWEEP_FRACTIONS = [1 / 25, 1 / 10, 1 / 5, 1 / 2, 1]
+ACCLIMATION_PRIOR = 16
 
 
 def build_parser():
@@ -51,7 +54,42 @@ def build_parser():
     p.add_argument("--expand_synth_boxes", action="store_true", help="(not built) real-blur datasets")
     p.add_argument("--mode_one_norm", action="store_true", help="Test-time batch-norm: every layer mixes the image's statistics "
                    "into its running ones (single model only, as in the reference)")
+    p.add_argument("--acclimate_norm", action="store_true", help="(this repo) Online batch-norm statistics, the reference layer's "
+                   "acclimation_mode: every layer folds the image's statistics into its running ones, on the device, and normalises "
+                   "with the updated ones; the detector drifts toward the stream it sees (single model, fp32)")
+    p.add_argument("--acclimation_momentum", type=float, default=None, help="(this repo) with --acclimate_norm: the exponential "
+                   "average's factor; unset: the cumulative average over --acclimation_prior + images seen")
+    p.add_argument("--acclimation_prior", type=int, default=None, help="(this repo) with --acclimate_norm: the batches the source "
+                   "statistics count for (default %d: the first image weighs 1/%d, as in --mode_one_norm)" % (ACCLIMATION_PRIOR, ACCLIMATION_PRIOR + 1))
+    p.add_argument("--acclimation_carry_over", action="store_true", help="(this repo) with --acclimate_norm: the statistics run on "
+                   "through the passes (the 15 sweep cells) instead of starting every pass from the source statistics")
     return p
+
+
+def reject_acclimation_conflicts(args):
+    """--acclimate_norm's refusals, before anything is built."""
+    on = getattr(args, "acclimate_norm", False)
+    if not on:
+        for flag in ("acclimation_momentum", "acclimation_prior", "acclimation_carry_over"):
+            value = getattr(args, flag, None)
+            if value is not None and value is not False:
+                raise SystemExit("--%s needs --acclimate_norm: it sets how the online batch-norm statistics are averaged and nothing "
+                                 "else reads it" % flag)
+        return
+    if getattr(args, "mode_one_norm", False):
+        raise SystemExit("--acclimate_norm with --mode_one_norm: both replace the batch-norm layers' statistics and the layer runs "
+                         "one of them (acclimation wins in the reference's layer); choose one")
+    if getattr(args, "use_ensemble", False):
+        raise SystemExit("--acclimate_norm with --use_ensemble: online statistics are built for a single model; four detectors "
+                         "routed per image would each adapt to the part of the stream they are handed")
+    if getattr(args, "amp", False):
+        raise SystemExit("--amp with --acclimate_norm: the online batch-norm kernel (dib_bn_acclimate_nhwc) and its tolerances are "
+                         "fp32; a bf16 lane for it is not built")
+    if args.acclimation_prior is not None and args.acclimation_prior < 0:
+        raise SystemExit("--acclimation_prior %d: the number of batches the source statistics count for cannot be negative" % args.acclimation_prior)
+    m = args.acclimation_momentum
+    if m is not None and not (0.0 <= m <= 1.0):
+        raise SystemExit("--acclimation_momentum %g: the exponential average's factor lies in [0, 1]" % m)
 
 
 def _load(model, path):
@@ -73,6 +111,7 @@ def main(args):
     from . import kernel_choices
     kernel_choices.use_shipped_kernel_choices()      # shipped MIOpen / TunableOp choices, private copy per process (kernel_choices.py)
     reject_out_of_scope(args)
+    reject_acclimation_conflicts(args)
     if getattr(args, "deblur_first", False) and not getattr(args, "deblurer_model_location", None):
         raise SystemExit("--deblur_first needs --deblurer_model_location: a DeepDeblur experiment directory (models/model-<N>.pt) or a "
                          "checkpoint file; the reference's default is a path on its author's disk and nothing is downloaded "
@@ -92,7 +131,7 @@ def main(args):
         # reference scores sharp images against the sweep's labels without saying so
         print("Warning: neither --gpu_blur nor --cpu_blur: the sweep will score UNBLURRED images.")
 
-    def detector(path=None, mode_one=False):
+    def detector(path=None, mode_one=False, acclimate=False):
         m = _load(fasterrcnn_resnet50_fpn(num_classes=91, pretrained=args.pretrained, pretrained_backbone=False,
                                           warp_internally=args.warp_in_model, **detector_size_kwargs(args)), path).to(device)
         if mode_one:                                                    # reference evaluate.py:234-237, before DDP wrapping
@@ -100,6 +139,21 @@ def main(args):
             m = utils.convert_to_custom_batch_norm(m, batch_norm_to_use=BatchNorm2d)
             m = utils.set_batch_norm_N(m, 16)
             m = utils.set_batch_norm_mode1(m, True)
+        if acclimate:                                                   # the reference's helpers around its layer's acclimation_mode
+            from .models.batchnorm import BatchNorm2d
+            prior = ACCLIMATION_PRIOR if args.acclimation_prior is None else args.acclimation_prior
+            m = utils.convert_to_custom_batch_norm(m, batch_norm_to_use=BatchNorm2d)
+            m = utils.set_batch_norm_N(m, prior)
+            if args.acclimation_momentum is None:
+                m = utils.set_batch_momentum_zero(m)                    # cumulative: image k of a pass weighs 1 / (prior + k)
+            else:
+                m = utils.set_batch_momentum(m, args.acclimation_momentum)
+            m = utils.set_batch_norm_acclimation_mode(m, True)
+            m = utils.copy_BN_stats_to_old(m)                           # what every pass starts from (engine.evaluate restores it)
+            m.acclimate_norm = True                                     # engine.evaluate: re-arm the layers after eval()
+            m.acclimation_carry_over = bool(args.acclimation_carry_over)
+            if args.distributed:
+                print("--acclimate_norm: every rank adapts to its own shard of the images (the statistics are not synchronised)")
         if not args.distributed:
             return m
         return torch.nn.parallel.DistributedDataParallel(m, device_ids=[args.gpu] if device.type == "cuda" else None,
@@ -117,7 +171,8 @@ def main(args):
             estimator.fc = nn.Linear(512, 4 if args.LEHE else 16)
             estimator = _load(estimator, args.blur_estimator_path).to(device)
     else:
-        model = detector(args.resume or args.model_path, mode_one=getattr(args, "mode_one_norm", False))
+        model = detector(args.resume or args.model_path, mode_one=getattr(args, "mode_one_norm", False),
+                         acclimate=getattr(args, "acclimate_norm", False))
 
     deblurer = build_deblurer(args, device)
     deblur_kw = dict(deblur_first=bool(getattr(args, "deblur_first", False)), deblurer=deblurer)

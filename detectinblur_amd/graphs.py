@@ -13,17 +13,25 @@ import torch
 class StaticGraph(object):
     """The graph holds RAW POINTERS to everything its launches read.  What lives outside the capture's memory pool and is not
     kept alive by anybody else (cached anchors, lookup tables) must therefore be among `fn`'s outputs: `self.out` is the
-    reference that keeps it alive as long as the graph (generalized_rcnn._trunk returns its anchors for that reason)."""
+    reference that keeps it alive as long as the graph (generalized_rcnn._trunk returns its anchors for that reason).
+    `state`: a callable that lists the tensors `fn` UPDATES in place (online batch-norm statistics, --acclimate_norm).  The
+    warm-up calls run `fn` for real, the capture does not: the listed tensors are put back, in place, to what they held before
+    the warm-up, so that building a graph leaves no trace in the state and the first replay is the first update."""
 
-    def __init__(self, fn, example, warmup=2, pool=None):
+    def __init__(self, fn, example, warmup=2, pool=None, state=None):
         self.static_in = example.clone(memory_format=torch.preserve_format)
         cur = torch.cuda.current_stream(example.device)
+        kept = [(t, t.clone()) for t in (state() if state is not None else ())]
         side = torch.cuda.Stream(device=example.device)
         side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                fn(self.static_in)
-        cur.wait_stream(side)
+        try:
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    fn(self.static_in)
+        finally:
+            cur.wait_stream(side)
+            for t, before in kept:
+                t.copy_(before)
         torch.cuda.synchronize(example.device)
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: a DataLoader's pin-memory thread allocating host memory must not invalidate the capture
@@ -46,8 +54,8 @@ class GraphCache(object):
     input shapes after the transform (the grid `python -m detectinblur_amd.kernel_choices --fill --shapes coco-eval` fills the kernel-choice data for); a cache smaller
     than that would evict and recapture (three forward passes each) all through an evaluation."""
 
-    def __init__(self, fn, limit=64, capture_after=2):
-        self.fn, self.limit, self.capture_after = fn, limit, capture_after
+    def __init__(self, fn, limit=64, capture_after=2, state=None):
+        self.fn, self.limit, self.capture_after, self.state = fn, limit, capture_after, state
         self.graphs, self.seen, self.pool = {}, {}, None
 
     def clear(self):
@@ -70,7 +78,7 @@ class GraphCache(object):
         if self.pool is None:
             self.pool = torch.cuda.graph_pool_handle()
         try:
-            g = StaticGraph(self.fn, x, pool=self.pool)
+            g = StaticGraph(self.fn, x, pool=self.pool, **({} if self.state is None else {"state": self.state}))
         except Exception as e:      # noqa: BLE001 -- e.g. an op that synchronises; stay correct, stay eager
             import sys
             sys.stderr.write("detectinblur_amd.graphs: capture failed for %s (%s: %s); running eagerly\n" % (key[0], type(e).__name__, e))

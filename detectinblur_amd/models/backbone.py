@@ -672,7 +672,8 @@ def _wide_out(x, conv):
 
 # Test-time batch-norm statistics (`--mode_one_norm`, models/batchnorm.py): the convolution runs unfolded (the statistics are the
 # input's), then ONE call does statistics + normalisation + residual + ReLU in place on its output (dib_bn_mode_one_nhwc: three
-# launches, ~3 passes).  Set to False to run the reference's torch expression instead (A/B runs).
+# launches, ~3 passes).  Online statistics (`--acclimate_norm`) take the same route through dib_bn_acclimate_nhwc, which also writes
+# the layer's running statistics and counter.  Set to False to run the reference's torch expression instead (A/B runs).
 FUSE_TEST_TIME_BN = True
 
 
@@ -688,7 +689,7 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
             weight, shift = _folded(conv, bn, x.dtype)
         y = _WideOut1x1.apply(x, weight) if _wide_out(x, conv) else conv1x1(x, weight, None, conv)
         return bias_act(y, shift, residual, relu)
-    if isinstance(bn, BatchNorm2d) and bn.mode_one:
+    if isinstance(bn, BatchNorm2d) and (bn.mode_one or bn.acclimation_mode):
         # the same convolution detours as the folded path (same MIOpen / hipBLASLt shapes), on the unfolded weight
         return bn.forward_fused_(conv1x1(x, conv.weight, conv.bias, conv), residual, relu)
     if x.dtype != conv.weight.dtype:

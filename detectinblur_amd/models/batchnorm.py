@@ -12,9 +12,19 @@ Two ways to the same values:
   * torch: everything else (CPU, planar tensors, gradients), a line-for-line restatement of the reference's forward, bit for
     bit its values (tests/test_mode_one_norm.py).
 
-With `mode_one` off the module is `torch.nn.BatchNorm2d`.  The reference's `acclimation_mode` is not offered: no driver
-reaches it.  `last_path` records which of the two ran last ("hip" / "torch"), for tests and A/B runs; the switch for those
-is backbone.FUSE_TEST_TIME_BN.
+`acclimation_mode` (reference models/batchnorm.py:142-157; `evaluate.py --acclimate_norm`) is the online form: the layer first
+folds the statistics of the batch it sees into its running statistics -- F.batch_norm(..., training=True, a) with a the momentum
+or, with `momentum = None` in training mode, 1 / num_batches_tracked after its bump -- and then normalises with the updated
+running statistics.  It wins over `mode_one` where both are set, as in the reference.  The same two ways:
+
+  * HIP (dib_bn_acclimate_nhwc): under the conditions above, with the running statistics and the counter updated IN PLACE on the
+    device (a captured graph's replays and the pipelined loop carry the state; nothing is read on the host).  A training layer's
+    counter must therefore be on the device; one value per channel goes to the torch path, which raises torch's error;
+  * torch: the reference's forward, statement for statement, `self.num_batches_tracked = self.num_batches_tracked + 1` included --
+    a rebinding that a captured graph must never see, so this path refuses to run under capture.
+
+With both flags off the module is `torch.nn.BatchNorm2d`.  `last_path` records which of the two ran last ("hip" / "torch"), for
+tests and A/B runs; the switch for those is backbone.FUSE_TEST_TIME_BN.
 """
 import torch
 import torch.nn.functional as F
@@ -25,6 +35,7 @@ class BatchNorm2d(nn.BatchNorm2d):
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None):
         super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
         self.mode_one = False
+        self.acclimation_mode = False
         self.last_path = None
 
     # ---- which path ------------------------------------------------------------------------------------------------------------
@@ -39,9 +50,17 @@ class BatchNorm2d(nn.BatchNorm2d):
                                         or (self.bias is not None and self.bias.requires_grad)
                                         or (residual is not None and residual.requires_grad)):
             return False
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            return False                # the reference bumps num_batches_tracked first: the torch path does that
         dev = x.device
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            # the reference bumps num_batches_tracked first: mode one's torch path does that; the acclimation kernel does it itself,
+            # in place, on a counter that lives on the device
+            if not (self.acclimation_mode and self.num_batches_tracked.device == dev):
+                return False
+        if self.acclimation_mode:
+            if x.shape[0] * x.shape[2] * x.shape[3] < 2:
+                return False            # torch raises for one value per channel in training mode: the torch path shows that error
+            if self.momentum is not None and not (0.0 <= float(self.momentum) <= 1.0):
+                return False
         for t in (self.weight, self.bias, self.running_mean, self.running_var):
             if t is not None and not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
                 return False
@@ -106,8 +125,58 @@ class BatchNorm2d(nn.BatchNorm2d):
         var_to_use = source_stat_factor * passed_running_var + batch_stat_factor * input_var
         return F.batch_norm(input, mean_to_use, var_to_use, self.weight, self.bias, False, 0.0, self.eps)
 
+    def _acclimate_hip_(self, x, residual=None, relu=False, stats=None):
+        """x = act(bn(x) (+ residual)) in place with running_mean, running_var and (training mode) num_batches_tracked updated in
+        place on the device (dib_bn_acclimate_nhwc).  `stats`: a [4, C] fp32 CUDA tensor that receives the batch mean, the unbiased
+        batch variance and the updated running pair."""
+        from .. import _lib
+        N, C, H, W = x.shape
+        npix = N * H * W
+        l = _lib.lib()
+        nbytes = l.dib_bn_mode_one_workspace_bytes(npix, C)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=x.device)      # the caching allocator (a graph's pool under capture)
+        nbt = self.num_batches_tracked
+        bump = bool(self.training and self.track_running_stats and nbt is not None)
+        nb_dev = nbt.data_ptr() if nbt is not None and nbt.is_cuda else None
+        momentum = -1.0 if self.momentum is None else float(self.momentum)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        _lib.check(l.dib_bn_acclimate_nhwc(x.data_ptr(), ptr(residual), npix, C, ptr(self.weight), ptr(self.bias),
+                                           self.running_mean.data_ptr(), self.running_var.data_ptr(), nb_dev, int(bump), momentum,
+                                           float(self.eps), int(bool(relu)), ws.data_ptr(), ws.numel() * 4, ptr(stats), _lib.stream_of(x)))
+        self.last_path = "hip"
+        return x
+
+    def _acclimate_torch(self, input):
+        """reference models/batchnorm.py:105-157 for acclimation_mode, statement for statement."""
+        if input.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("BatchNorm2d: the torch path of acclimation_mode rebinds num_batches_tracked and cannot be captured into a graph")
+        self._check_input_dim(input)
+        if self.momentum is None:
+            exponential_average_factor = 0.0
+        else:
+            exponential_average_factor = self.momentum
+        if self.training and self.track_running_stats:
+            if self.num_batches_tracked is not None:
+                self.num_batches_tracked = self.num_batches_tracked + 1
+                if self.momentum is None:
+                    exponential_average_factor = 1.0 / float(self.num_batches_tracked)
+                else:
+                    exponential_average_factor = self.momentum
+        passed_running_mean = self.running_mean if not self.training or self.track_running_stats else None
+        passed_running_var = self.running_var if not self.training or self.track_running_stats else None
+        self.last_path = "torch"
+        # two runs through batch_norm: one takes the batch's statistics and updates the running ones (training set to True), the
+        # other computes the output from the running statistics so far (training set to False)
+        _ = F.batch_norm(input, passed_running_mean, passed_running_var, self.weight, self.bias, True, exponential_average_factor, self.eps)
+        output = F.batch_norm(input, passed_running_mean, passed_running_var, self.weight, self.bias, False, 0.0, self.eps)
+        return output
+
     # ---- entry points ----------------------------------------------------------------------------------------------------------
     def forward(self, input):
+        if self.acclimation_mode:
+            if self._hip_ok(input):
+                return self._acclimate_hip_(input.clone(memory_format=torch.channels_last))
+            return self._acclimate_torch(input)
         if not self.mode_one:
             return super().forward(input)
         if self._hip_ok(input):
@@ -116,7 +185,10 @@ class BatchNorm2d(nn.BatchNorm2d):
 
     def forward_fused_(self, x, residual=None, relu=False):
         """act(self(x) (+ residual)), in place on x where the HIP path applies (x: a fresh convolution output nothing else holds)."""
-        if self.mode_one and self._hip_ok(x, residual):
+        if self.acclimation_mode:
+            if self._hip_ok(x, residual):
+                return self._acclimate_hip_(x, residual, relu)
+        elif self.mode_one and self._hip_ok(x, residual):
             return self._mode_one_hip_(x, residual, relu)
         y = self(x)
         if residual is not None:

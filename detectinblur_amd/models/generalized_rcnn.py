@@ -79,6 +79,16 @@ class GeneralizedRCNN(nn.Module):
         # anchors and the warps' base-coordinate tables are read through raw pointers: they travel with the outputs (see _trunk)
         return tuple(fl) + tuple(self.rpn.propose_static(fl, anchors, self._sizes[x.shape[0]])) + (anchors,) + tuple(tables)
 
+    def _trunk_state(self):
+        """What a trunk pass updates in place: the running statistics and counters of acclimating batch-norm layers
+        (--acclimate_norm, models/batchnorm.py).  A captured trunk writes them through their addresses at every replay, which is
+        how the state travels from image to image; graphs.StaticGraph puts them back after its warm-up passes."""
+        out = []
+        for m in self.backbone.modules():
+            if getattr(m, "acclimation_mode", False):
+                out += [t for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
+        return out
+
     def _sync_graphs_with_weights(self, cache):
         """A captured trunk reads the FPN / RPN parameters through their live pointers and the trunk's convolutions through the
         cached batch-norm folds (backbone._folded).  Before every replay: (1) if any parameter or buffer of the trunk was
@@ -115,11 +125,11 @@ class GeneralizedRCNN(nn.Module):
         if warp_params is None:
             cache = self.__dict__.get("_trunk_graphs")
             if cache is None:
-                cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk)
+                cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk, state=self._trunk_state)
         else:
             cache = self.__dict__.get("_warped_trunk_graphs")
             if cache is None:
-                cache = self.__dict__["_warped_trunk_graphs"] = GraphCache(self._trunk_warped)
+                cache = self.__dict__["_warped_trunk_graphs"] = GraphCache(self._trunk_warped, state=self._trunk_state)
             self.__dict__["_warp_params"] = warp_params
             for key in self.__dict__.get("_warp_plans", {}).get(tuple(x.shape), ()):
                 self._fill_warp_mats(key)
@@ -159,7 +169,7 @@ class GeneralizedRCNN(nn.Module):
         sizes[n].copy_(host, non_blocking=True)
         cache = self.__dict__.get("_trunk_graphs")
         if cache is None:
-            cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk)
+            cache = self.__dict__["_trunk_graphs"] = GraphCache(self._trunk, state=self._trunk_state)
         self._sync_graphs_with_weights(cache)
         outs = cache(x)
         return {"images": batch, "original_sizes": original_sizes, "outs": outs, "feat_names": list(self._feat_names)}

@@ -5,6 +5,9 @@
   * collate_fn, distributed helpers, meters      reference utils.py:474-785  (below)
   * convert_to_custom_batch_norm, set_batch_norm_N, set_batch_norm_mode1
                                                  reference utils.py:59-77, :122-135, :150-162 (--mode_one_norm)
+  * turn_batch_norm_on, set_batch_momentum_zero, set_batch_momentum, set_batch_norm_acclimation_mode, copy_BN_stats_to_old,
+    reset_batch_norm_values                      reference utils.py:80-120, :136-148, :193-217 (--acclimate_norm), with this
+                                                 repo's restore_BN_stats_from_old (in place) and acclimation_on_device
   * create_unique_color_float, compute_colors_for_labels, overlay_boxes_torch
                                                  reference utils.py:279-353  (detection overlays: overlay.py, HIP on a GPU)
 """
@@ -88,6 +91,131 @@ def set_batch_norm_N(model, N):
             module.num_batches_tracked = module.num_batches_tracked + N
     _drop_trunk_caches(model)
     return model
+
+
+# ---------------------------------------------------------------------------------------------
+# online batch-norm statistics (--acclimate_norm): the reference's helpers around the layer's acclimation_mode
+# ---------------------------------------------------------------------------------------------
+
+def _each_bn(model, fn):
+    """the reference's walk (utils.py:80-217): `fn` on `model` itself if it is a batch-norm layer, then on every batch-norm layer
+    under it, children in reverse order.  Returns `model`."""
+    if _is_bn(model):
+        fn(model)
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = _each_bn(module, fn)
+        if _is_bn(module):
+            fn(module)
+    return model
+
+
+def turn_batch_norm_on(model):
+    """Every batch-norm layer under `model` into training mode (reference utils.py:80-92); everything else stays as it is, so a
+    detector in eval mode keeps its inference forward pass.  Captured trunks stay: a graph holds launches, not flags, and
+    engine.evaluate re-arms a model it has just put into eval mode with this call before every pass."""
+    def on(m):
+        m.train()
+    return _each_bn(model, on)
+
+
+def set_batch_momentum_zero(model):
+    """`momentum = None` on every batch-norm layer: the cumulative average (reference utils.py:94-106)."""
+    def none(m):
+        m.momentum = None
+    _each_bn(model, none)
+    _drop_trunk_caches(model)                # a captured launch holds the factor's rule as an argument
+    return model
+
+
+def set_batch_momentum(model, momentum):
+    """`momentum = momentum` on every batch-norm layer: the exponential average (reference utils.py:136-148)."""
+    def put(m):
+        m.momentum = momentum
+    _each_bn(model, put)
+    _drop_trunk_caches(model)
+    return model
+
+
+def set_batch_norm_acclimation_mode(model, flag):
+    """`acclimation_mode = flag` on every batch-norm layer (reference utils.py:108-120)."""
+    def put(m):
+        m.acclimation_mode = flag
+    _each_bn(model, put)
+    _drop_trunk_caches(model)
+    return model
+
+
+_OLD_STATS = (("old_running_mean", "running_mean"), ("old_running_var", "running_var"), ("old_num_batches_tracked", "num_batches_tracked"))
+
+
+def copy_BN_stats_to_old(model):
+    """Snapshot: old_running_mean / old_running_var / old_num_batches_tracked = clones of the running statistics on every
+    batch-norm layer under `model` (reference utils.py:193-205, whose layers register the three as buffers; here they are
+    buffers outside the state_dict, so that a checkpoint keeps the keys of torch's layer)."""
+    def snapshot(m):
+        for old, cur in _OLD_STATS:
+            m._buffers.pop(old, None)
+            m.register_buffer(old, getattr(m, cur).clone(), persistent=False)
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = copy_BN_stats_to_old(module)
+        if _is_bn(module):
+            snapshot(module)
+    _drop_trunk_caches(model)                # the trunk's pointer watch counts buffers
+    return model
+
+
+def restore_BN_stats_from_old(model):
+    """The inverse of copy_BN_stats_to_old (this repo): the snapshot is copied IN PLACE into the existing running_mean, running_var
+    and num_batches_tracked -- never a new tensor, a captured graph holds their addresses -- on the current stream, without a
+    synchronisation.  A layer without a snapshot is an error."""
+    def restore(m):
+        for old, cur in _OLD_STATS:
+            if getattr(m, old, None) is None:
+                raise RuntimeError("restore_BN_stats_from_old: no snapshot on this layer (copy_BN_stats_to_old comes first)")
+            with torch.no_grad():
+                getattr(m, cur).copy_(getattr(m, old), non_blocking=True)
+    return _each_bn(model, restore)
+
+
+def reset_batch_norm_values(model):
+    """reset_running_stats() on every batch-norm layer under `model` (reference utils.py:207-217): in place."""
+    for name, module in reversed(model._modules.items()):
+        if len(list(module.children())) > 0:
+            model._modules[name] = reset_batch_norm_values(module)
+        if _is_bn(module):
+            module.reset_running_stats()
+    return model
+
+
+def acclimation_on_device(model, device):
+    """Whether every acclimating batch-norm layer under `model` can keep its state on `device` through the HIP path
+    (models/batchnorm.BatchNorm2d._hip_ok's conditions that do not depend on the input): engine.evaluate decides once per pass
+    whether the trunk may be captured -- a layer on the torch path rebinds num_batches_tracked, which a graph must never see."""
+    from .models import backbone
+    from .models.batchnorm import BatchNorm2d
+    layers = [m for m in model.modules() if _is_bn(m) and getattr(m, "acclimation_mode", False)]
+    if not layers:
+        return True
+    if not (backbone.FUSE_TEST_TIME_BN and device.type == "cuda"):
+        return False
+    for m in layers:
+        if not isinstance(m, BatchNorm2d) or m.num_features % 4 or m.running_mean is None or m.running_var is None:
+            return False
+        if m.training and not m.track_running_stats:
+            return False
+        if m.momentum is not None and not (0.0 <= float(m.momentum) <= 1.0):
+            return False
+        for t in (m.weight, m.bias, m.running_mean, m.running_var):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                return False
+        if any(p is not None and p.requires_grad and torch.is_grad_enabled() for p in (m.weight, m.bias)):
+            return False
+        nbt = m.num_batches_tracked
+        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.numel() == 1 and (nbt.is_cuda or not m.training)):
+            return False
+    return True
 
 
 # ---------------------------------------------------------------------------------------------

@@ -512,6 +512,28 @@ int dib_bn_mode_one_nhwc(float *x_dev, const float *residual_dev, long long n_pi
                          void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Online batch-norm statistics, the reference layer's `acclimation_mode` (models/batchnorm.py:142-157; `evaluate.py
+ * --acclimate_norm`): the layer first folds the statistics of the batch it sees into its running statistics, as
+ * F.batch_norm(..., training=True, a) does, then normalises with the UPDATED running statistics, as
+ * F.batch_norm(..., training=False) does.  Per channel, every product and sum rounded separately:
+ *   n   = *num_batches_dev + (bump ? 1 : 0)                              (stored back when bump)
+ *   a   = momentum >= 0 ? momentum : bump ? float(1.0 / double(n)) : 0   (negative momentum: cumulative average)
+ *   rm' = (1 - a) * rm + a * mean_b,   rv' = (1 - a) * rv + a * M2 / (n_pix - 1)        (the UNBIASED batch variance)
+ *   x   = act(x * scale[c] + shift[c] (+ residual)),  scale = w / sqrt(rv' + eps),  shift = b - rm' * scale.
+ * Arguments as dib_bn_mode_one_nhwc (same layout, alignment and workspace: dib_bn_mode_one_workspace_bytes), except:
+ * running_mean_dev / running_var_dev are WRITTEN (rm', rv'), each channel's pair by the one lane that read it;
+ * num_batches_dev (one int64 on the device, 8-byte aligned; may be NULL without bump and with momentum >= 0) is written when
+ * bump is set -- by one lane of the LAST of the three launches, while the old value is read in the second only, so no read can
+ * follow the write; stats_dev, optional: [4][C] floats -- batch mean, unbiased batch variance, rm', rv'.
+ * n_pix < 2 is DIB_EINVAL (torch raises for one value per channel in training mode).  Three launches, no atomics, no host
+ * synchronisation, nothing kept between calls but the layer's own state: deterministic and capturable into a graph, whose
+ * replays then carry the state forward.
+ * ------------------------------------------------------------------------------------- */
+int dib_bn_acclimate_nhwc(float *x_dev, const float *residual_dev, long long n_pix, int C, const float *weight_dev, const float *bias_dev,
+                          float *running_mean_dev, float *running_var_dev, long long *num_batches_dev, int bump, float momentum,
+                          float eps, int relu, void *workspace_dev, size_t workspace_bytes, float *stats_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * AugMix on the device (reference transforms.py:68-79, augmix/augment_and_mix.py:123-185), from plans drawn on the host
  * (transforms.AugMix): per image three chains of up to three ops, Pillow's semantics on uint8 images, then the reference's
  * float64 mix with the COCO mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225), written as fp16.
