@@ -57,6 +57,7 @@ class TapTables:
         self.K, self.count = K, count
         self.large = bool(large)      # compacted for the large LDS window (include/dib.h: DIB_COMPACT_LARGE_WINDOW): the blur must be told
         self.vruns = bool(vruns)      # carries the vertical-run groups DIB_ACC_FAST16 walks (DIB_COMPACT_VRUNS)
+        self.dtype = torch.float16    # of the PSFs the weights' bits came from (compact_psfs sets it): dib_rl_deconvolve is told
         self.words = table_words(K)
         if self.words == 0:
             raise ValueError("PSF must be 128 or 256 wide, got %d" % K)
@@ -224,6 +225,7 @@ def compact_psfs(psfs, normalize, large_window=False, vruns=False):
             ptrs.append(a)
         tabs = TapTables(K, len(keep), first.device, large_window, vruns and K == 128 and dt == torch.float16)
         tabs._pin = keep   # alive until the tables die
+        tabs.dtype = dt
         _lib.check(l.dib_psf_compact_list(_lib.ptr_array(ptrs), _DT[dt], len(keep), K, flags,
                                           tabs.buf.data_ptr(), _stream(first.device)))
         return tabs
@@ -236,6 +238,7 @@ def compact_psfs(psfs, normalize, large_window=False, vruns=False):
         raise TypeError("PSF dtype %s not supported (float16 / float32)" % stack.dtype)
     B, K = stack.shape[0], stack.shape[1]
     tabs = TapTables(K, B, stack.device, large_window, vruns and K == 128 and stack.dtype == torch.float16)
+    tabs.dtype = stack.dtype
     _lib.check(l.dib_psf_compact(stack.data_ptr(), _DT[stack.dtype], B, K, flags,
                                  tabs.buf.data_ptr(), _stream()))
     return tabs

@@ -461,7 +461,8 @@ class EvaluationResult(object):
 def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None, vanilla_eval=False, blurring_images=False,
              gpu_blur=False, expand_target_boxes=False, deblur_first=False, deblurer=None, use_custom_image_norm=False,
              use_ensemble=False, ensemble_models=None, blur_estimator=None, add_noise=False, noise_level=0.001, add_block=False,
-             add_jpeg_artifact=False, image_output_folder=None, LEHE=False, epoch_number=None, blur_acc_mode="bitexact"):
+             add_jpeg_artifact=False, image_output_folder=None, LEHE=False, epoch_number=None, blur_acc_mode="bitexact",
+             deconvolve_first=False, deconvolver=None):
     """reference engine.py:220-416.  Runs the detector (or the routed ensemble) over the loader, scores the
     detections against the dataset's COCO ground truth (boxes replaced by the expanded ones under
     `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
@@ -469,6 +470,10 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     `deblur_first` / `deblurer` (reference :319-322): after the blur, the corruptions and the box growth, the first image of the batch
     is replaced by `deblurer.deblur_(image)` (models/deblur.py: DeepDeblur's MSResNet, fp32, or Half when the deblurrer was built so)
     when the pass blurs or is the vanilla one.
+    `deconvolve_first` / `deconvolver` (this repo, --deconvolve_first): in the same place, in a pass that blurs, the first image of the
+    batch -- when its blur_dict says it was blurred -- is replaced by `deconvolver.deconvolve_(image, blur_dict, psf, tables)`
+    (models/deconvolve.py: Richardson-Lucy with the image's own PSF, the tap table the blur has just read; fp32 out).  The ground truth
+    grown by `expand_target_boxes` stays the blurred image's.
     A model that evaluate.py marked for online batch-norm statistics (`acclimate_norm`, with `acclimation_carry_over`): after eval() its
     batch-norm layers go back into training mode (utils.turn_batch_norm_on) and, unless the statistics carry over, the pass starts
     from the snapshot (utils.restore_BN_stats_from_old, in place).  The graphed trunk and the pipelined loop carry the state: the
@@ -486,6 +491,11 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     deblurring = bool(deblur_first) and (blurring_images or vanilla_eval)
     if deblurring and deblurer is None:
         raise ValueError("evaluate(deblur_first=True) needs a deblurer (models.deblur.Deblurer)")
+    deconvolving = bool(deconvolve_first) and blurring_images
+    if deconvolving and deconvolver is None:
+        raise ValueError("evaluate(deconvolve_first=True) needs a deconvolver (models.deconvolve.Deconvolver)")
+    if deconvolving and deblurring:
+        raise ValueError("evaluate: deblur_first and deconvolve_first both replace the image in front of the detector; choose one")
     jpeg_compressor = None
     if add_jpeg_artifact:                                                # reference :248-254
         from .models.jpeg import DiffJPEG
@@ -587,6 +597,11 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 # fp32 (a Half deblurrer's: Half), as the reference hands it on: the estimator's batcher, the detector and the
                 # overlay all read this image, and all of them take either type (Half is what the blur hands them anyway).
                 images_GPU[0] = deblurer.deblur_(images_GPU[0])
+            if deconvolving and blur_dicts[0]["blurring"]:
+                # the same place and the same image: 2 x iterations HIP launches on the current stream, no synchronisation.  The staged
+                # tables hold the blurring PSFs in batch order, so image 0's table is table 0; without staged tables (the CPU, mixed
+                # canvases) the stage compacts the PSF itself.  fp32 out, like the deblurrer's.
+                images_GPU[0] = deconvolver.deconvolve_(images_GPU[0], blur_dicts[0], psfs_GPU[0], tables, 0)
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
             est = None
             if use_ensemble and blur_estimator is not None:                  # reference :354-366 (the routing itself: below)

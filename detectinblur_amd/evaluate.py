@@ -14,7 +14,9 @@ evaluate.py:240-243, engine.py:319-322; models/deblur.py): the image stays on th
 `--deblur_precision half` runs that stage as DeepDeblur's `--precision half` does (the module and its pyramid in Half) and hands the
 detector a Half image; `--amp` is independent of it and leaves the deblurrer alone.
 `--acclimate_norm` (this repo's flag for the reference layer's `acclimation_mode`, models/batchnorm.py:142-157, and the helpers of
-its utils.py:80-217): online batch-norm statistics, updated on the device image by image (models/batchnorm.py, engine.evaluate)."""
+its utils.py:80-217): online batch-norm statistics, updated on the device image by image (models/batchnorm.py, engine.evaluate).
+`--deconvolve_first` (this repo): Richardson-Lucy deconvolution with the image's own, known PSF in front of the detector in every sweep
+cell (models/deconvolve.py; `--deconvolve_iterations N`): the non-blind upper bound next to `--deblur_first`'s blind baseline."""
 import os
 import argparse
 
@@ -32,6 +34,7 @@ from .train import _seed_worker, add_shared_flags, detector_size_kwargs, get_tra
 SWEEP_PARAMS = [0.005, 0.001, 0.00005]
 SWEEP_FRACTIONS = [1 / 25, 1 / 10, 1 / 5, 1 / 2, 1]
 ACCLIMATION_PRIOR = 16
+DECONVOLVE_ITERATIONS, MAX_DECONVOLVE_ITERATIONS = 30, 1000      # models/deconvolve.py's DEFAULT_ITERATIONS / MAX_ITERATIONS
 
 
 def build_parser():
@@ -63,7 +66,50 @@ def build_parser():
                    "statistics count for (default %d: the first image weighs 1/%d, as in --mode_one_norm)" % (ACCLIMATION_PRIOR, ACCLIMATION_PRIOR + 1))
     p.add_argument("--acclimation_carry_over", action="store_true", help="(this repo) with --acclimate_norm: the statistics run on "
                    "through the passes (the 15 sweep cells) instead of starting every pass from the source statistics")
+    p.add_argument("--deconvolve_first", action="store_true", help="(this repo) Deconvolve every blurred image with its own, known PSF "
+                   "(Richardson-Lucy on the blur's forward model, on the device) before detecting: the non-blind upper bound of "
+                   "--deblur_first.  Needs --gpu_blur.  With --expand_target_boxes the ground truth is still grown for the blurred image")
+    p.add_argument("--deconvolve_iterations", type=int, default=DECONVOLVE_ITERATIONS, metavar="N", action=_StoreGiven, help="(this repo) with --deconvolve_first: "
+                   "Richardson-Lucy iterations, 1..%d (default %d); more sharpen further and amplify noise and JPEG residue further"
+                   % (MAX_DECONVOLVE_ITERATIONS, DECONVOLVE_ITERATIONS))
     return p
+
+
+class _StoreGiven(argparse.Action):
+    """stores the value and notes, as <dest>_given, that the flag was on the command line (its default says nothing about that)"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
+def reject_deconvolution_conflicts(args):
+    """--deconvolve_first's refusals, before anything is built."""
+    n = getattr(args, "deconvolve_iterations", DECONVOLVE_ITERATIONS)
+    if not getattr(args, "deconvolve_first", False):
+        if getattr(args, "deconvolve_iterations_given", False):
+            raise SystemExit("--deconvolve_iterations needs --deconvolve_first: it is the iteration count of that stage and nothing else "
+                             "reads it")
+        return
+    if getattr(args, "deblur_first", False):
+        raise SystemExit("--deconvolve_first with --deblur_first: both replace the image in front of the detector (the blind network "
+                         "and the known-PSF iteration); choose one")
+    if getattr(args, "vanilla_eval", False):
+        raise SystemExit("--deconvolve_first with --vanilla_eval: the clean pass has no PSF, the flag would do nothing")
+    if getattr(args, "cpu_blur", False) or not getattr(args, "gpu_blur", False):
+        raise SystemExit("--deconvolve_first needs --gpu_blur (and not --cpu_blur): the iteration inverts the sparse correlation of "
+                         "--gpu_blur; the FFT path of --cpu_blur rescales every image to its own minimum and maximum, which is not "
+                         "that forward model")
+    if not (1 <= n <= MAX_DECONVOLVE_ITERATIONS):
+        raise SystemExit("--deconvolve_iterations %d: the iteration count lies in 1..%d" % (n, MAX_DECONVOLVE_ITERATIONS))
+
+
+def build_deconvolver(args):
+    """the Deconvolver of `--deconvolve_first` with `--deconvolve_iterations`, or None"""
+    if not getattr(args, "deconvolve_first", False):
+        return None
+    from .models.deconvolve import Deconvolver
+    return Deconvolver(iterations=getattr(args, "deconvolve_iterations", DECONVOLVE_ITERATIONS))
 
 
 def reject_acclimation_conflicts(args):
@@ -112,6 +158,7 @@ def main(args):
     kernel_choices.use_shipped_kernel_choices()      # shipped MIOpen / TunableOp choices, private copy per process (kernel_choices.py)
     reject_out_of_scope(args)
     reject_acclimation_conflicts(args)
+    reject_deconvolution_conflicts(args)
     if getattr(args, "deblur_first", False) and not getattr(args, "deblurer_model_location", None):
         raise SystemExit("--deblur_first needs --deblurer_model_location: a DeepDeblur experiment directory (models/model-<N>.pt) or a "
                          "checkpoint file; the reference's default is a path on its author's disk and nothing is downloaded "
@@ -176,6 +223,8 @@ def main(args):
 
     deblurer = build_deblurer(args, device)
     deblur_kw = dict(deblur_first=bool(getattr(args, "deblur_first", False)), deblurer=deblurer)
+    deconvolver = build_deconvolver(args)
+    deconvolve_kw = dict(deconvolve_first=deconvolver is not None, deconvolver=deconvolver)
 
     def loader_for(tf):
         ds, _ = get_coco(args.data_path, "val", tf, synthetic=synthetic, with_masks=getattr(args, "with_masks", False))
@@ -211,7 +260,7 @@ def main(args):
                            blurring_images=True, gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                            use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
                            add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode,
-                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **deblur_kw, **ens_kw)
+                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **deblur_kw, **deconvolve_kw, **ens_kw)
             results["P%dE%d" % (param_index, fraction_index - 1)] = out
             if utils.is_main_process():
                 log_coco_stats(writer, "P" + str(param_index), out, fraction_index)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes, the bf16 epilogues dib_bias_act_bf16_nhwc, dib_bias_act_mask_bf16_nhwc, dib_relu_mask_backward_bf16, dib_add_relu_mask_bf16, dib_scatter_add_bf16_nhwc, dib_fpn_topdown_merge_bf16_nhwc, dib_stem_pool_forward_bf16 / _backward_bf16, dib_squint_warp_forward / _backward, dib_overlay_rgb8): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
+#define DIB_ABI_VERSION 7 /* 7: no kernel traps any more (later additions, new symbols only: dib_bn_mode_one_nhwc, dib_bn_mode_one_workspace_bytes, dib_augmix, dib_augmix_buffer_bytes, dib_augmix_workspace_bytes, the bf16 epilogues dib_bias_act_bf16_nhwc, dib_bias_act_mask_bf16_nhwc, dib_relu_mask_backward_bf16, dib_add_relu_mask_bf16, dib_scatter_add_bf16_nhwc, dib_fpn_topdown_merge_bf16_nhwc, dib_stem_pool_forward_bf16 / _backward_bf16, dib_squint_warp_forward / _backward, dib_overlay_rgb8, the deblurrer's dib_deblur_* entry points, dib_rl_deconvolve): DIB_ETIMEOUT, dib_device_status ("Device status" below); dib_blur_step takes an optional caller workspace through dib_blur_step_ws and bounds its private buffers; 6: + dib_sparse_blur_normalized (the blur with the input transform's float + normalise + zero-padded batch as its store phase); dib_blur_step runs compaction + blur as ONE launch where the shapes allow it (same results, same signature); 5: + dib_blur_step / dib_blur_step_release (DIB_ECAPTURE, DIB_STEP_PSFS_COMPLETE), dib_normalize_resize_pad, dib_fold_bn_multi, dib_scale_rows_multi, dib_box_match / _encode_matched / _decode / _pool / _labels, dib_topk_levels, dib_det_candidates, dib_bias_act_transpose, the large LDS window; 4: + dib_bias_act_mask_nhwc, dib_relu_mask_backward, dib_add_relu_mask, dib_scatter_add_nhwc, dib_fpn_topdown_merge_nhwc, dib_stem_pool_forward / _backward, dib_post_ops, dib_jpeg_roundtrip; 2: tap-table buffers carry no scheduler trailer any more; 3: tables carry a second
                              per-tap offset array (sizes come from dib_tap_table_bytes as before)          */
 
 /* error codes */
@@ -682,6 +682,27 @@ int dib_deblur_finish(const float *in_dev, const float *bias_dev, float *out_dev
 int dib_deblur_pyramid_f16(const void *in_dev, int dtype, int H, int W, int n_scales, void *const *levels_dev, float *work_dev, void *stream);
 int dib_deblur_shuffle_concat_f16(const void *in_dev, const float *bias_dev, void *out_dev, int h, int w, void *stream);
 int dib_deblur_finish_f16(const void *in_dev, const float *bias_dev, void *out_dev, int H, int W, int Hp, int Wp, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Non-blind deconvolution with the blur's own forward model (this library's addition; `evaluate.py --deconvolve_first`): Richardson-
+ * Lucy on one C x H x W planar image y_dev of `dtype` (the blurred, possibly corrupted image) with the tap table the blur read
+ * (dib_psf_compact with normalize = 1; psf_dtype = the dtype of the PSF it was compacted from: fp16 or fp32 weight bits; either LDS
+ * window geometry).  With o = K / 2 - 1 and the taps {(r_t, c_t, w_t)} of the table, not re-normalised:
+ *     (A  x)[i, j] = sum_t w_t x[m (i - (r_t - o)), m (j - (c_t - o))]     dib_sparse_blur's operator: m is its padding rule (reflect /
+ *                                                                          zero / replicate by K, H, W) with the wrap row and column
+ *     (A* u)[i, j] = sum_t w_t u[m'(i + (r_t - o)), m'(j + (c_t - o))]     offsets negated; m' = the same rule without the wrap
+ *     x_0 = y;   q = y / max(A x_k, eps);   x_{k+1} = clamp(x_k * (A* q), 0, 1);   out_dev = x_iterations, fp32 C x H x W
+ * All arithmetic fp32 (y read as fp32), every sweep accumulates from 0 with fused multiply-adds, taps in table order.  A pixel with
+ * y == 0 and A x == 0 gives q = 0: finite input never produces NaN or Inf.  Two launches per iteration on `stream` (sweep A with the
+ * ratio as its epilogue, sweep A* with multiply and clamp); work_dev: 2 C H W floats (q and the spare plane x_k alternates through
+ * with out_dev, so that the result ends in out_dev for odd and even counts).  No allocation, no host synchronisation, no atomics:
+ * deterministic and capturable.  y_dev, out_dev and work_dev must not overlap.
+ * DIB_EINVAL (nothing launched): null pointer, unknown dtype, K not 128 / 256, C, H or W < 1, iterations outside 1..1000, eps <= 0,
+ * overlapping buffers.  DIB_ESHAPE: where dib_sparse_blur refuses the image (K = 128 and H or W == 64 with neither below 64), or
+ * C H W >= 2^31 - 1.
+ * ------------------------------------------------------------------------------------- */
+int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
+                      int psf_dtype, int K, int iterations, float eps, void *stream);
 
 #ifdef __cplusplus
 }
