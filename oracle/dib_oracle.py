@@ -1422,3 +1422,158 @@ def to_bf16_bits(v):
 
 def from_bf16_bits(b):
     return (np.asarray(b, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+# --------------------------------------------------------------------------------------
+# A23 the detector's and estimator's input transform: float64 / IEEE float32 reference for csrc/dib_epilogue.hip
+#     (normalize_pad_kernel, normalize_resize_pad_kernel behind dib_normalize_pad / dib_normalize_resize_pad /
+#     dib_normalize_resize_crop; reference engine.py:107-110, models/net_transforms.py:112-121, :151-175, :226-247,
+#     engine_blur_estimator.py:217)
+# --------------------------------------------------------------------------------------
+# Plain numpy on the host, no torch, nothing of the package.  What is exact in the kernels is stated exactly: the normalised source
+# pixel (two correctly rounded float32 operations), the sampling position and its weights (float32), the quantisation, the
+# padding.  The one approximate stage, the four-term interpolation, is evaluated in float64 from those float32 operands, and the
+# magnitude the error bound scales with is returned with it.  tests/test_input_transform_reference.py holds this section to torch
+# on the CPU and to tests/golden/net_transforms.npz.
+
+TRANSFORM_UNIT = 2.0 ** -24            # half an ulp of a float32 in [1, 2): one rounding of a value of magnitude <= 1
+TRANSFORM_BOUND = 5.0                  # in units of TRANSFORM_UNIT * M: product, inner sum, outer product, outer sum, each at most one
+                                       # unit of a magnitude the convex weights keep <= M, and one for the second-order terms; the
+                                       # contracted form has fewer roundings
+
+
+def transform_quantize(x):
+    """`(img * 255).type(torch.uint8).type(torch.half) / 255` as ATen evaluates it on Half: a = half(float(x) * 255f),
+    k = uint8(trunc(a)), q = half(float(k) / 255f).  Domain: finite x >= 0 with half(x * 255) < 256."""
+    x = np.asarray(x, dtype=np.float16)
+    a = (x.astype(np.float32) * np.float32(255.0)).astype(np.float16)
+    if not (np.isfinite(x) & (x >= 0) & (a < 256)).all():
+        raise ValueError("transform_quantize: outside the documented domain")
+    k = np.trunc(a.astype(np.float32)).astype(np.uint8)
+    return (k.astype(np.float32) / np.float32(255.0)).astype(np.float16)
+
+
+def transform_normalize(image, mean, std, quantize=False):
+    """[3, H, W] float16 / float32 -> float32 n = (float32(p) - mean32) / std32, each operation ONE float32 rounding."""
+    image = np.asarray(image)
+    if image.dtype not in (np.float16, np.float32) or image.ndim != 3 or image.shape[0] != 3:
+        raise ValueError("transform_normalize: 3 x H x W float16 / float32 images")
+    if quantize:
+        image = transform_quantize(image)
+    m = np.asarray(mean, dtype=np.float64).astype(np.float32).reshape(3, 1, 1)
+    s = np.asarray(std, dtype=np.float64).astype(np.float32).reshape(3, 1, 1)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        return (image.astype(np.float32) - m) / s
+
+
+def transform_positions(n_in, n_out, contracted=True):
+    """One axis of the bilinear resize (align_corners=False, the scale recomputed from the integer sizes).  Returns
+    (i, ip, l0, l1, s): the first source index, whether a second one follows it (the edge clamp), the float32 weights of the two
+    exactly as the kernel forms them, and the real-arithmetic position s = (n_in / n_out)(dst + 0.5) - 0.5 clamped to
+    [0, n_in - 1] in float64.  r32 * (dst + 0.5) is exact in float64, so `contracted` (the kernel's fmaf, ATen's arithmetic on the
+    GPU) is one rounding of r32 * (dst + 0.5) - 0.5; the uncontracted form rounds the product first."""
+    r32 = np.float32(n_in) / np.float32(n_out)
+    t = np.arange(n_out, dtype=np.float64) + 0.5
+    if contracted:
+        s32 = (np.float64(r32) * t - 0.5).astype(np.float32)
+    else:
+        s32 = (np.float64(r32) * t).astype(np.float32) - np.float32(0.5)
+    s32 = np.where(s32 < 0, np.float32(0.0), s32).astype(np.float32)
+    i = s32.astype(np.int64)
+    ip = (i < n_in - 1).astype(np.int64)
+    l1 = s32 - i.astype(np.float32)                       # exact
+    l0 = np.float32(1.0) - l1
+    s = np.clip((np.float64(n_in) / np.float64(n_out)) * t - 0.5, 0.0, float(n_in - 1))
+    return i, ip, l0, l1, s
+
+
+def _real_positions(n_in, n_out):
+    s = transform_positions(n_in, n_out)[4]
+    i = np.minimum(np.floor(s).astype(np.int64), n_in - 1)
+    return i, (i < n_in - 1).astype(np.int64), 1.0 - (s - i), s - i
+
+
+def _bilinear64(n, hpos, wpos):
+    """l0h (l0w p00 + l1w p01) + l1h (l0w p10 + l1w p11) in float64, and M = max |p00, p01, p10, p11| per element."""
+    n = np.asarray(n, dtype=np.float64)
+    (h, hp, l0h, l1h), (w, wp, l0w, l1w) = hpos, wpos
+    l0h, l1h = (np.asarray(v, dtype=np.float64).reshape(-1, 1) for v in (l0h, l1h))
+    l0w, l1w = (np.asarray(v, dtype=np.float64).reshape(1, -1) for v in (l0w, l1w))
+    p00, p01 = n[:, h][:, :, w], n[:, h][:, :, w + wp]
+    p10, p11 = n[:, h + hp][:, :, w], n[:, h + hp][:, :, w + wp]
+    with np.errstate(invalid="ignore", over="ignore"):      # 0 * inf and inf - inf are data here
+        v = l0h * (l0w * p00 + l1w * p01) + l1h * (l0w * p10 + l1w * p11)
+        M = np.fmax(np.fmax(np.abs(p00), np.abs(p01)), np.fmax(np.abs(p10), np.abs(p11)))
+    return v, np.where(np.isnan(p00) | np.isnan(p01) | np.isnan(p10) | np.isnan(p11), np.nan, M)
+
+
+def transform_bilinear_real64(n, Ho, Wo):
+    """Bilinear interpolation of n [3, H, W] at the real-arithmetic positions, all in float64: what F.interpolate(mode="bilinear",
+    align_corners=False, size=(Ho, Wo)) computes in float64."""
+    return _bilinear64(n, _real_positions(n.shape[1], Ho), _real_positions(n.shape[2], Wo))[0]
+
+
+def input_transform64(images, means, stds, out_sizes, Hp, Wp, crop=False, quantize=False, contracted=True):
+    """The batch [B, 3, Hp, Wp] of dib_normalize_pad (out_sizes None), dib_normalize_resize_pad and dib_normalize_resize_crop for a
+    list of 3 x H x W float16 / float32 images, per-image means / stds (rounded to float32 first), per-image (Ho, Wo).  pad: image k
+    resized sits in the top-left corner, +0.0 around it; `crop`: the top-left Hp x Wp corner of every resized image.  Returns
+      v      float64: for an image with (Ho, Wo) == (H, W) the float32 n itself, otherwise the interpolation in float64 from the
+             float32 weights and the float32 n; +0.0 in the padding
+      M      float64: max |p00, p01, p10, p11| per element (|n| at unit scale, 0 in the padding)
+      exact  bool: unit-scale and padding elements, where a kernel has to give the bits of float32(v)."""
+    B = len(images)
+    means = np.asarray(means, dtype=np.float64).reshape(B, 3)
+    stds = np.asarray(stds, dtype=np.float64).reshape(B, 3)
+    v = np.zeros((B, 3, Hp, Wp), dtype=np.float64)
+    M = np.zeros((B, 3, Hp, Wp), dtype=np.float64)
+    exact = np.ones((B, 3, Hp, Wp), dtype=bool)
+    for k, image in enumerate(images):
+        n = transform_normalize(image, means[k], stds[k], quantize)
+        H, W = n.shape[1:]
+        Ho, Wo = (H, W) if out_sizes is None else (int(out_sizes[k][0]), int(out_sizes[k][1]))
+        if crop and (Hp > Ho or Wp > Wo):
+            raise ValueError("input_transform64: image %d is (resized) smaller than the crop" % k)
+        if not crop and (Ho > Hp or Wo > Wp):
+            raise ValueError("input_transform64: image %d is (resized) larger than the batch" % k)
+        if (Ho, Wo) == (H, W):
+            val, mag = n.astype(np.float64), np.abs(n.astype(np.float64))
+        else:
+            val, mag = _bilinear64(n, transform_positions(H, Ho, contracted)[:4], transform_positions(W, Wo, contracted)[:4])
+        h, w = min(Ho, Hp), min(Wo, Wp)
+        v[k, :, :h, :w], M[k, :, :h, :w] = val[:, :h, :w], mag[:, :h, :w]
+        exact[k, :, :h, :w] = (Ho, Wo) == (H, W)
+    return v, M, exact
+
+
+def _f32_class(a):
+    return np.where(np.isnan(a), 3, np.where(a == np.inf, 1, np.where(a == -np.inf, 2, 0)))
+
+
+def input_transform_compare(got, v, M, exact):
+    """The one comparison of a kernel's float32 batch with input_transform64's (v, M, exact).  Asserts, in order: NaN, +inf and
+    -inf exactly where float32(v) has them; unit-scale and padding elements bit-equal (-0 is not +0); every other finite element
+    within TRANSFORM_BOUND * 2**-24 * M of v.  Non-finite reference elements may be at most 10 % of the batch.  Returns the peak
+    deviation of the bounded elements in units of 2**-24 * M."""
+    got = np.ascontiguousarray(got)
+    assert got.dtype == np.float32 and got.shape == v.shape == M.shape == exact.shape, (got.dtype, got.shape, v.shape)
+    with np.errstate(over="ignore"):
+        v32 = v.astype(np.float32)
+    special = _f32_class(v32) != 0
+    assert special.sum() <= 0.1 * special.size, "inputs: %d of %d reference elements are not finite" % (special.sum(), special.size)
+    wrong = np.argwhere(_f32_class(got) != _f32_class(v32))
+    assert len(wrong) == 0, "NaN / inf class differs at %d elements, first %s: got %r, reference %r" % (
+        len(wrong), tuple(int(j) for j in wrong[0]), got[tuple(wrong[0])], v32[tuple(wrong[0])])
+    sel = exact & ~special
+    wrong = np.argwhere(sel & (got.view(np.uint32) != v32.view(np.uint32)))
+    assert len(wrong) == 0, "unit-scale / padding bits differ at %d elements, first %s: got %r, reference %r" % (
+        len(wrong), tuple(int(j) for j in wrong[0]), got[tuple(wrong[0])], v32[tuple(wrong[0])])
+    sel = ~exact & ~special
+    err = np.abs(got.astype(np.float64)[sel] - v[sel])
+    unit = TRANSFORM_UNIT * M[sel]
+    wrong = err > TRANSFORM_BOUND * unit
+    if wrong.any():
+        at = tuple(int(j) for j in np.argwhere(sel)[np.argmax(wrong)])
+        raise AssertionError("%d elements beyond %g * 2^-24 * M, first %s: got %r, reference %r, M %r" % (
+            wrong.sum(), TRANSFORM_BOUND, at, got[at], v[at], M[at]))
+    live = unit > 0
+    return float((err[live] / unit[live]).max()) if live.any() else 0.0
