@@ -18,6 +18,9 @@
 // CU's 160 KB of LDS, at most 80 scalar registers): while one workgroup waits at a window's fill and its two barriers, the others'
 // tap loops have the CU.  tests/test_deconvolve_resources.py holds every instantiation to this budget.
 // No scratch, no atomics, no allocation; every launch is an ordinary stream-ordered one (capturable).
+// Contract: y is finite (in [0, 1]) and eps large enough that y / eps is.  A lane past a segment's end, or whose tap lies in another
+// window of its segment, multiplies weight 0 by a live window word instead of skipping it: a NaN or Inf there would reach output
+// pixels that the definition's taps do not connect it with.  Not tested, not guarded.
 #include <hip/hip_fp16.h>
 
 #include "dib_common.h"

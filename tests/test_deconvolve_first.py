@@ -146,8 +146,14 @@ def reference(name, iterations, y_dtype="float16", psf_dtype="float16"):
     """(x_N in float64, tolerance) of a case: y is the Half image, or (y_dtype float32) its fp32 blur"""
     cs = case(name, psf_dtype)
     y = cs["y16"] if y_dtype == "float16" else ref_sweep(cs["truth"], cs["taps"], cs["K"], False).astype(np.float32)
-    want = ref_rl(y, cs["taps"], cs["K"], iterations)
-    d = float(np.abs(ref_rl(y, cs["taps"], cs["K"], iterations, dtype=np.float32).astype(np.float64) - want).max())
+    return reference_of(y, cs["taps"], cs["K"], iterations)
+
+
+def reference_of(y, taps, K, iterations, eps=EPS):
+    """(x_N in float64, tolerance, d) of one image and tap list: the tolerance rule of this module's docstring, stated once (the
+    geometry cases of tests/test_deconvolve_geometry.py take it from here)"""
+    want = ref_rl(y, taps, K, iterations, eps)
+    d = float(np.abs(ref_rl(y, taps, K, iterations, eps, dtype=np.float32).astype(np.float64) - want).max())
     return want, max(8 * d, iterations * 2.0 ** -20), d
 
 
