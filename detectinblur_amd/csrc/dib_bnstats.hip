@@ -19,7 +19,11 @@
 // three launches: bn_acclimate_finalize_kernel folds the batch's mean and UNBIASED variance into the running statistics with
 // factor a (the momentum, or 1 / num_batches_tracked after its bump), writes them back and normalises with the updated pair;
 // the bumped counter is stored by the apply launch (bn_apply_bump_kernel), behind every read of the old value.
-#include "dib_common.h"
+//
+// Host side: both entry points refuse what only they can be given wrong and then call bn_run, which holds the refusals they
+// share, the geometry, the workspace layout (bn_workspace, also behind the size query) and the three launches; an entry point
+// supplies its finalize launch and says whether the apply launch bumps the counter.
+#include "dib_eltwise_vec.h"      // host side only: misaligned, grid_1d, launch
 
 namespace dib {
 
@@ -282,8 +286,49 @@ static BnGeom bn_geometry(long long npix, int C) {
   return g;
 }
 
-// workspace: scale [C], shift [C], slice means [S][C], slice M2 [S][C] (floats)
-static size_t bn_workspace_floats(const BnGeom &g) { return 2 * (size_t)g.C + 2 * (size_t)g.S * g.C; }
+// The workspace layout, stated once: scale [C], shift [C], slice means [S][C], slice M2 [S][C] (floats).  The size query calls
+// this with a null base and reads only `floats`.
+struct BnWorkspace {
+  float *scale, *shift, *ws_mean, *ws_m2;
+  size_t floats;
+};
+
+static BnWorkspace bn_workspace(const BnGeom &g, void *base) {
+  const size_t C = (size_t)g.C, slices = (size_t)g.S * C;
+  float *ws = (float *)base;
+  return {ws, ws + C, ws + 2 * C, ws + 2 * C + slices, 2 * C + 2 * slices};
+}
+
+template <bool RES, bool RELU>
+static int bn_apply(float *x, const BnWorkspace &w, const float *res, long long n4, int C4, long long *bump_nbt, void *stream) {
+  // grid_1d caps the grid at 2^30 workgroups; both kernels stride over what is left, which takes more than 2^38 elements
+  if (bump_nbt) return launch(bn_apply_bump_kernel<RES, RELU>, grid_1d(n4), stream, x, w.scale, w.shift, res, n4, C4, bump_nbt);
+  return launch(bn_apply_kernel<RES, RELU>, grid_1d(n4), stream, x, w.scale, w.shift, res, n4, C4);
+}
+
+// The host sequence of both entry points (`who`): the refusals they share, then the three launches on `stream`.
+//   align_rule   the entry point's sentence about alignment (acclimation's names its counter as well)
+//   finalize     (grid, block, stream, g, workspace) -> launches the entry point's finalize kernel
+//   bump_nbt     the counter that the apply launch bumps (bn_apply_bump_kernel), or null (bn_apply_kernel)
+template <class Finalize>
+static int bn_run(const char *who, const char *align_rule, float *x_dev, const float *residual_dev, long long n_pix, int C,
+                  const float *running_mean_dev, const float *running_var_dev, int relu, long long *bump_nbt, void *workspace_dev,
+                  size_t workspace_bytes, void *stream, Finalize finalize) {
+  if (n_pix <= 0 || C <= 0 || (C % 4) != 0 || C / 4 > 65535LL * 64) { set_error("%s: needs n_pix > 0 and C %% 4 == 0 (C = %d)", who, C); return DIB_EINVAL; }
+  if (!x_dev || !running_mean_dev || !running_var_dev || !workspace_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
+  if (misaligned({x_dev, residual_dev, workspace_dev})) { set_error("%s: %s", who, align_rule); return DIB_EINVAL; }
+  const BnGeom g = bn_geometry(n_pix, C);
+  const BnWorkspace w = bn_workspace(g, workspace_dev);
+  const size_t need = w.floats * sizeof(float);
+  if (workspace_bytes < need) { set_error("%s: workspace of %zu bytes, needs %zu", who, workspace_bytes, need); return DIB_EINVAL; }
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned chunks = (unsigned)((g.Q + g.QB - 1) / g.QB);
+  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)g.S, chunks), dim3(BN_THREADS), 0, s, (const float4 *)x_dev, g, w.ws_mean, w.ws_m2);
+  finalize(dim3((unsigned)((C + 63) / 64)), dim3(64 * BN_FIN_LANES), s, g, w);
+  const auto apply = residual_dev ? (relu ? bn_apply<true, true> : bn_apply<true, false>)
+                                  : (relu ? bn_apply<false, true> : bn_apply<false, false>);
+  return apply(x_dev, w, residual_dev, n_pix * (C / 4), C / 4, bump_nbt, stream);      // one float4 per lane
+}
 
 }  // namespace dib
 
@@ -291,82 +336,38 @@ using namespace dib;
 
 extern "C" size_t dib_bn_mode_one_workspace_bytes(long long n_pix, int C) {
   if (n_pix <= 0 || C <= 0 || (C % 4) != 0) return 0;
-  return bn_workspace_floats(bn_geometry(n_pix, C)) * sizeof(float);
+  return bn_workspace(bn_geometry(n_pix, C), nullptr).floats * sizeof(float);
 }
 
 extern "C" int dib_bn_mode_one_nhwc(float *x_dev, const float *residual_dev, long long n_pix, int C, const float *weight_dev,
                                     const float *bias_dev, const float *running_mean_dev, const float *running_var_dev,
                                     const long long *num_batches_dev, long long num_batches, float eps, int relu, void *workspace_dev,
                                     size_t workspace_bytes, float *stats_dev, void *stream) {
-  if (n_pix <= 0 || C <= 0 || (C % 4) != 0 || C / 4 > 65535LL * 64) { set_error("dib_bn_mode_one_nhwc: needs n_pix > 0 and C %% 4 == 0 (C = %d)", C); return DIB_EINVAL; }
-  if (!x_dev || !running_mean_dev || !running_var_dev || !workspace_dev) { set_error("dib_bn_mode_one_nhwc: null pointer"); return DIB_EINVAL; }
-  if ((((uintptr_t)x_dev | (uintptr_t)residual_dev | (uintptr_t)workspace_dev) & 15) != 0) {
-    set_error("dib_bn_mode_one_nhwc: x, residual and workspace must be 16-byte aligned");
-    return DIB_EINVAL;
-  }
-  if (!num_batches_dev && num_batches < 0) { set_error("dib_bn_mode_one_nhwc: negative num_batches_tracked"); return DIB_EINVAL; }
-  const BnGeom g = bn_geometry(n_pix, C);
-  const size_t need = bn_workspace_floats(g) * sizeof(float);
-  if (workspace_bytes < need) { set_error("dib_bn_mode_one_nhwc: workspace of %zu bytes, needs %zu", workspace_bytes, need); return DIB_EINVAL; }
-  float *ws = (float *)workspace_dev;
-  float *scale = ws, *shift = ws + C, *ws_mean = ws + 2 * (size_t)C, *ws_m2 = ws_mean + (size_t)g.S * C;
-  const hipStream_t s = (hipStream_t)stream;
-  const unsigned chunks = (unsigned)((g.Q + g.QB - 1) / g.QB);
-  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)g.S, chunks), dim3(BN_THREADS), 0, s, (const float4 *)x_dev, g, ws_mean, ws_m2);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64 * BN_FIN_LANES), 0, s, g, ws_mean, ws_m2, weight_dev,
-                     bias_dev, running_mean_dev, running_var_dev, num_batches_dev, num_batches, eps, scale, shift, stats_dev);
-  const long long n4 = n_pix * (C / 4);
-  long long blocks = (n4 + 255) / 256;         // one float4 per lane, as the streaming kernels of dib_eltwise.hip
-  if (blocks > 0x7fffffffLL) blocks = 0x7fffffffLL;
-#define DIB_LAUNCH(RES, RELU)                                                                                                  \
-  hipLaunchKernelGGL((bn_apply_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev, (const float4 *)scale, \
-                     (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4)
-  if (residual_dev) { if (relu) DIB_LAUNCH(true, true); else DIB_LAUNCH(true, false); }
-  else { if (relu) DIB_LAUNCH(false, true); else DIB_LAUNCH(false, false); }
-#undef DIB_LAUNCH
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  static const char who[] = "dib_bn_mode_one_nhwc";
+  if (!num_batches_dev && num_batches < 0) { set_error("%s: negative num_batches_tracked", who); return DIB_EINVAL; }
+  return bn_run(who, "x, residual and workspace must be 16-byte aligned", x_dev, residual_dev, n_pix, C, running_mean_dev, running_var_dev,
+                relu, nullptr, workspace_dev, workspace_bytes, stream,
+                [&](dim3 grid, dim3 block, hipStream_t s, const BnGeom &g, const BnWorkspace &w) {
+                  hipLaunchKernelGGL(bn_finalize_kernel, grid, block, 0, s, g, w.ws_mean, w.ws_m2, weight_dev, bias_dev, running_mean_dev,
+                                     running_var_dev, num_batches_dev, num_batches, eps, w.scale, w.shift, stats_dev);
+                });
 }
 
 extern "C" int dib_bn_acclimate_nhwc(float *x_dev, const float *residual_dev, long long n_pix, int C, const float *weight_dev,
                                      const float *bias_dev, float *running_mean_dev, float *running_var_dev, long long *num_batches_dev,
                                      int bump, float momentum, float eps, int relu, void *workspace_dev, size_t workspace_bytes,
                                      float *stats_dev, void *stream) {
-  if (n_pix <= 0 || C <= 0 || (C % 4) != 0 || C / 4 > 65535LL * 64) { set_error("dib_bn_acclimate_nhwc: needs n_pix > 0 and C %% 4 == 0 (C = %d)", C); return DIB_EINVAL; }
-  if (n_pix < 2) { set_error("dib_bn_acclimate_nhwc: more than one value per channel is needed to fold an unbiased variance in"); return DIB_EINVAL; }
-  if (!x_dev || !running_mean_dev || !running_var_dev || !workspace_dev) { set_error("dib_bn_acclimate_nhwc: null pointer"); return DIB_EINVAL; }
-  if (bump && !num_batches_dev) { set_error("dib_bn_acclimate_nhwc: bump without num_batches_dev"); return DIB_EINVAL; }
-  if (!(momentum <= 1.f)) { set_error("dib_bn_acclimate_nhwc: momentum above 1 (negative: cumulative average)"); return DIB_EINVAL; }
-  if ((((uintptr_t)x_dev | (uintptr_t)residual_dev | (uintptr_t)workspace_dev) & 15) != 0 || ((uintptr_t)num_batches_dev & 7) != 0) {
-    set_error("dib_bn_acclimate_nhwc: x, residual and workspace must be 16-byte aligned, num_batches_dev 8-byte aligned");
-    return DIB_EINVAL;
-  }
-  const BnGeom g = bn_geometry(n_pix, C);
-  const size_t need = bn_workspace_floats(g) * sizeof(float);
-  if (workspace_bytes < need) { set_error("dib_bn_acclimate_nhwc: workspace of %zu bytes, needs %zu", workspace_bytes, need); return DIB_EINVAL; }
-  float *ws = (float *)workspace_dev;
-  float *scale = ws, *shift = ws + C, *ws_mean = ws + 2 * (size_t)C, *ws_m2 = ws_mean + (size_t)g.S * C;
-  const hipStream_t s = (hipStream_t)stream;
-  const unsigned chunks = (unsigned)((g.Q + g.QB - 1) / g.QB);
-  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)g.S, chunks), dim3(BN_THREADS), 0, s, (const float4 *)x_dev, g, ws_mean, ws_m2);
-  hipLaunchKernelGGL(bn_acclimate_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64 * BN_FIN_LANES), 0, s, g, ws_mean, ws_m2,
-                     weight_dev, bias_dev, running_mean_dev, running_var_dev, (const long long *)num_batches_dev, bump ? 1 : 0, momentum, eps,
-                     scale, shift, stats_dev);
-  const long long n4 = n_pix * (C / 4);
-  long long blocks = (n4 + 255) / 256;
-  if (blocks > 0x7fffffffLL) blocks = 0x7fffffffLL;
-#define DIB_LAUNCH(RES, RELU)                                                                                                       \
-  do {                                                                                                                              \
-    if (bump)                                                                                                                       \
-      hipLaunchKernelGGL((bn_apply_bump_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev,               \
-                         (const float4 *)scale, (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4, num_batches_dev);   \
-    else                                                                                                                            \
-      hipLaunchKernelGGL((bn_apply_kernel<RES, RELU>), dim3((unsigned)blocks), dim3(256), 0, s, (float4 *)x_dev,                    \
-                         (const float4 *)scale, (const float4 *)shift, (const float4 *)residual_dev, n4, C / 4);                    \
-  } while (0)
-  if (residual_dev) { if (relu) DIB_LAUNCH(true, true); else DIB_LAUNCH(true, false); }
-  else { if (relu) DIB_LAUNCH(false, true); else DIB_LAUNCH(false, false); }
-#undef DIB_LAUNCH
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  static const char who[] = "dib_bn_acclimate_nhwc";
+  static const char align_rule[] = "x, residual and workspace must be 16-byte aligned, num_batches_dev 8-byte aligned";
+  // exactly one pixel: fewer is bn_run's shape refusal
+  if (n_pix == 1) { set_error("%s: more than one value per channel is needed to fold an unbiased variance in", who); return DIB_EINVAL; }
+  if (bump && !num_batches_dev) { set_error("%s: bump without num_batches_dev", who); return DIB_EINVAL; }
+  if (!(momentum <= 1.f)) { set_error("%s: momentum above 1 (negative: cumulative average)", who); return DIB_EINVAL; }
+  if (((uintptr_t)num_batches_dev & 7) != 0) { set_error("%s: %s", who, align_rule); return DIB_EINVAL; }
+  return bn_run(who, align_rule, x_dev, residual_dev, n_pix, C, running_mean_dev, running_var_dev, relu, bump ? num_batches_dev : nullptr,
+                workspace_dev, workspace_bytes, stream, [&](dim3 grid, dim3 block, hipStream_t s, const BnGeom &g, const BnWorkspace &w) {
+                  hipLaunchKernelGGL(bn_acclimate_finalize_kernel, grid, block, 0, s, g, w.ws_mean, w.ws_m2, weight_dev, bias_dev,
+                                     running_mean_dev, running_var_dev, (const long long *)num_batches_dev, bump ? 1 : 0, momentum, eps,
+                                     w.scale, w.shift, stats_dev);
+                });
 }

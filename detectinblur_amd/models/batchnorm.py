@@ -39,47 +39,67 @@ class BatchNorm2d(nn.BatchNorm2d):
         self.last_path = None
 
     # ---- which path ------------------------------------------------------------------------------------------------------------
-    def _hip_ok(self, x, residual=None):
+    def _hip_state_ok(self, dev):
+        """Whether this layer, as it is configured and where its state lives, may take the HIP path for inputs on `dev`: every
+        condition of that path that does not depend on the input.  `_hip_ok` adds the input's; utils.acclimation_on_device asks
+        this alone, before any input exists."""
         from . import backbone
-        if not (backbone.FUSE_TEST_TIME_BN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0
-                and x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15)):
+        if not (backbone.FUSE_TEST_TIME_BN and dev.type == "cuda"):
             return False
         if self.running_mean is None or self.running_var is None or (self.training and not self.track_running_stats):
             return False
-        if torch.is_grad_enabled() and (x.requires_grad or (self.weight is not None and self.weight.requires_grad)
-                                        or (self.bias is not None and self.bias.requires_grad)
-                                        or (residual is not None and residual.requires_grad)):
-            return False
-        dev = x.device
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+        nbt = self.num_batches_tracked
+        if self.training and self.track_running_stats and nbt is not None:
             # the reference bumps num_batches_tracked first: mode one's torch path does that; the acclimation kernel does it itself,
             # in place, on a counter that lives on the device
-            if not (self.acclimation_mode and self.num_batches_tracked.device == dev):
+            if not (self.acclimation_mode and nbt.device == dev):
                 return False
-        if self.acclimation_mode:
-            if x.shape[0] * x.shape[2] * x.shape[3] < 2:
-                return False            # torch raises for one value per channel in training mode: the torch path shows that error
-            if self.momentum is not None and not (0.0 <= float(self.momentum) <= 1.0):
-                return False
+        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.numel() == 1 and (nbt.device == dev or nbt.device.type == "cpu")):
+            return False
+        if self.acclimation_mode and self.momentum is not None and not (0.0 <= float(self.momentum) <= 1.0):
+            return False
         for t in (self.weight, self.bias, self.running_mean, self.running_var):
             if t is not None and not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
                 return False
-        nbt = self.num_batches_tracked
-        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.numel() == 1 and (nbt.device == dev or nbt.device.type == "cpu")):
+        return not (torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in (self.weight, self.bias)))
+
+    def _hip_ok(self, x, residual=None):
+        if not (x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] % 4 == 0 and x.numel() > 0
+                and x.is_contiguous(memory_format=torch.channels_last) and not (x.data_ptr() & 15) and self._hip_state_ok(x.device)):
             return False
-        return residual is None or (residual.shape == x.shape and residual.dtype == torch.float32 and residual.device == dev
+        if self.acclimation_mode and x.shape[0] * x.shape[2] * x.shape[3] < 2:
+            return False                # torch raises for one value per channel in training mode: the torch path shows that error
+        if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+            return False
+        return residual is None or (residual.shape == x.shape and residual.dtype == torch.float32 and residual.device == x.device
                                     and residual.is_contiguous(memory_format=torch.channels_last) and not (residual.data_ptr() & 15))
 
+    def _hip_method(self):
+        """The HIP method of the layer's mode: acclimation wins over mode one, as in the reference; None with both off."""
+        if self.acclimation_mode:
+            return self._acclimate_hip_
+        return self._mode_one_hip_ if self.mode_one else None
+
     # ---- the two paths ---------------------------------------------------------------------------------------------------------
-    def _mode_one_hip_(self, x, residual=None, relu=False, stats=None):
-        """x = act(bn(x) (+ residual)) in place (dib_bn_mode_one_nhwc).  `stats`: a [2, C] fp32 CUDA tensor that receives the mixed
-        mean and variance."""
+    def _hip_call_(self, entry, middle, x, residual, relu, stats):
+        """x = act(bn(x) (+ residual)) in place through `entry` (dib_bn_mode_one_nhwc or dib_bn_acclimate_nhwc); `middle`: what
+        their argument lists do not share, between running_var and eps."""
         from .. import _lib
         N, C, H, W = x.shape
         npix = N * H * W
         l = _lib.lib()
         nbytes = l.dib_bn_mode_one_workspace_bytes(npix, C)
         ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=x.device)      # the caching allocator (a graph's pool under capture)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        _lib.check(getattr(l, entry)(x.data_ptr(), ptr(residual), npix, C, ptr(self.weight), ptr(self.bias), self.running_mean.data_ptr(),
+                                     self.running_var.data_ptr(), *middle, float(self.eps), int(bool(relu)), ws.data_ptr(), ws.numel() * 4,
+                                     ptr(stats), _lib.stream_of(x)))
+        self.last_path = "hip"
+        return x
+
+    def _mode_one_hip_(self, x, residual=None, relu=False, stats=None):
+        """x = act(bn(x) (+ residual)) in place (dib_bn_mode_one_nhwc).  `stats`: a [2, C] fp32 CUDA tensor that receives the mixed
+        mean and variance."""
         nbt = self.num_batches_tracked
         if nbt is None:
             nb_dev, nb_host = None, 0
@@ -87,12 +107,7 @@ class BatchNorm2d(nn.BatchNorm2d):
             nb_dev, nb_host = nbt.data_ptr(), 0          # read on the device: no host synchronisation
         else:
             nb_dev, nb_host = None, int(nbt)             # a CPU tensor: read here (a captured graph keeps this value)
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        _lib.check(l.dib_bn_mode_one_nhwc(x.data_ptr(), ptr(residual), npix, C, ptr(self.weight), ptr(self.bias),
-                                          self.running_mean.data_ptr(), self.running_var.data_ptr(), nb_dev, nb_host, float(self.eps),
-                                          int(bool(relu)), ws.data_ptr(), ws.numel() * 4, ptr(stats), _lib.stream_of(x)))
-        self.last_path = "hip"
-        return x
+        return self._hip_call_("dib_bn_mode_one_nhwc", (nb_dev, nb_host), x, residual, relu, stats)
 
     def _mode_one_torch(self, input):
         """reference models/batchnorm.py:97-184 for mode_one (acclimation off), statement for statement."""
@@ -129,22 +144,11 @@ class BatchNorm2d(nn.BatchNorm2d):
         """x = act(bn(x) (+ residual)) in place with running_mean, running_var and (training mode) num_batches_tracked updated in
         place on the device (dib_bn_acclimate_nhwc).  `stats`: a [4, C] fp32 CUDA tensor that receives the batch mean, the unbiased
         batch variance and the updated running pair."""
-        from .. import _lib
-        N, C, H, W = x.shape
-        npix = N * H * W
-        l = _lib.lib()
-        nbytes = l.dib_bn_mode_one_workspace_bytes(npix, C)
-        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=x.device)      # the caching allocator (a graph's pool under capture)
         nbt = self.num_batches_tracked
         bump = bool(self.training and self.track_running_stats and nbt is not None)
         nb_dev = nbt.data_ptr() if nbt is not None and nbt.is_cuda else None
         momentum = -1.0 if self.momentum is None else float(self.momentum)
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        _lib.check(l.dib_bn_acclimate_nhwc(x.data_ptr(), ptr(residual), npix, C, ptr(self.weight), ptr(self.bias),
-                                           self.running_mean.data_ptr(), self.running_var.data_ptr(), nb_dev, int(bump), momentum,
-                                           float(self.eps), int(bool(relu)), ws.data_ptr(), ws.numel() * 4, ptr(stats), _lib.stream_of(x)))
-        self.last_path = "hip"
-        return x
+        return self._hip_call_("dib_bn_acclimate_nhwc", (nb_dev, int(bump), momentum), x, residual, relu, stats)
 
     def _acclimate_torch(self, input):
         """reference models/batchnorm.py:105-157 for acclimation_mode, statement for statement."""
@@ -173,23 +177,18 @@ class BatchNorm2d(nn.BatchNorm2d):
 
     # ---- entry points ----------------------------------------------------------------------------------------------------------
     def forward(self, input):
-        if self.acclimation_mode:
-            if self._hip_ok(input):
-                return self._acclimate_hip_(input.clone(memory_format=torch.channels_last))
-            return self._acclimate_torch(input)
-        if not self.mode_one:
+        hip = self._hip_method()
+        if hip is None:
             return super().forward(input)
         if self._hip_ok(input):
-            return self._mode_one_hip_(input.clone(memory_format=torch.channels_last))
-        return self._mode_one_torch(input)
+            return hip(input.clone(memory_format=torch.channels_last))
+        return self._acclimate_torch(input) if self.acclimation_mode else self._mode_one_torch(input)
 
     def forward_fused_(self, x, residual=None, relu=False):
         """act(self(x) (+ residual)), in place on x where the HIP path applies (x: a fresh convolution output nothing else holds)."""
-        if self.acclimation_mode:
-            if self._hip_ok(x, residual):
-                return self._acclimate_hip_(x, residual, relu)
-        elif self.mode_one and self._hip_ok(x, residual):
-            return self._mode_one_hip_(x, residual, relu)
+        hip = self._hip_method()
+        if hip is not None and self._hip_ok(x, residual):
+            return hip(x, residual, relu)
         y = self(x)
         if residual is not None:
             y = y + residual

@@ -190,32 +190,15 @@ def reset_batch_norm_values(model):
 
 
 def acclimation_on_device(model, device):
-    """Whether every acclimating batch-norm layer under `model` can keep its state on `device` through the HIP path
-    (models/batchnorm.BatchNorm2d._hip_ok's conditions that do not depend on the input): engine.evaluate decides once per pass
-    whether the trunk may be captured -- a layer on the torch path rebinds num_batches_tracked, which a graph must never see."""
-    from .models import backbone
+    """Whether every acclimating batch-norm layer under `model` can keep its state on `device` through the HIP path: the layer's
+    own answer (models/batchnorm.BatchNorm2d._hip_state_ok) plus what only this caller knows, that the layer is that class and that
+    its width suits the kernels.  engine.evaluate decides once per pass whether the trunk may be captured -- a layer on the torch
+    path rebinds num_batches_tracked, which a graph must never see."""
     from .models.batchnorm import BatchNorm2d
-    layers = [m for m in model.modules() if _is_bn(m) and getattr(m, "acclimation_mode", False)]
-    if not layers:
-        return True
-    if not (backbone.FUSE_TEST_TIME_BN and device.type == "cuda"):
-        return False
-    for m in layers:
-        if not isinstance(m, BatchNorm2d) or m.num_features % 4 or m.running_mean is None or m.running_var is None:
-            return False
-        if m.training and not m.track_running_stats:
-            return False
-        if m.momentum is not None and not (0.0 <= float(m.momentum) <= 1.0):
-            return False
-        for t in (m.weight, m.bias, m.running_mean, m.running_var):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                return False
-        if any(p is not None and p.requires_grad and torch.is_grad_enabled() for p in (m.weight, m.bias)):
-            return False
-        nbt = m.num_batches_tracked
-        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.numel() == 1 and (nbt.is_cuda or not m.training)):
-            return False
-    return True
+    if device.type == "cuda" and device.index is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())      # tensors name their card: "cuda" is the current one
+    return all(isinstance(m, BatchNorm2d) and m.num_features % 4 == 0 and m._hip_state_ok(device)
+               for m in model.modules() if _is_bn(m) and getattr(m, "acclimation_mode", False))
 
 
 # ---------------------------------------------------------------------------------------------

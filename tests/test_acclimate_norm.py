@@ -16,8 +16,6 @@ import importlib
 import io
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -440,25 +438,9 @@ def test_a_pass_without_the_flag_leaves_the_state_dict_alone(monkeypatch):
 
 # ---- kernel resources ----------------------------------------------------------------------------------------------------------------
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def test_no_kernel_of_the_statistics_file_uses_scratch():
-    if not os.path.isfile(HIPCC):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "detectinblur_amd", "csrc", "dib_bnstats.hip")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-c", src,
-                        "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    out, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    from tests._kernel_resources import kernel_resources
+    out = kernel_resources("dib_bnstats.hip")
     for frag, count in (("bn_partial_kernel", 1), ("bn_finalize_kernel", 1), ("bn_acclimate_finalize_kernel", 1), ("bn_apply_kernel", 4),
                         ("bn_apply_bump_kernel", 4)):
         assert len([n for n in out if frag in n]) == count, (frag, sorted(out))

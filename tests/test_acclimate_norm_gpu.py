@@ -16,7 +16,7 @@ import torch
 from detectinblur_amd import _lib, utils
 from detectinblur_amd.models import backbone
 from detectinblur_amd.models.batchnorm import BatchNorm2d
-from tests.test_mode_one_norm_gpu import _activation, _geometry_input, _relu_keeping_nan
+from tests.test_mode_one_norm_gpu import ALIGNED_16, _activation, _geometry_input, _relu_keeping_nan, check_refusals, refusal_case
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +180,69 @@ def test_one_pixel_is_refused_by_the_entry_point_and_raises_torchs_error_through
     with torch.no_grad(), pytest.raises(ValueError, match="more than 1 value per channel"):
         bn(x)
     assert bn.last_path != "hip"
+
+
+def test_entry_point_refusals_name_their_fault_and_launch_nothing():
+    base, tensors, rows = refusal_case(torch.device("cuda"), bump=1, momentum=0.1)
+    aligned = ALIGNED_16 + ", num_batches_dev 8-byte aligned"
+    rows = [(what, change, code, aligned if fragment == ALIGNED_16 else fragment) for what, change, code, fragment in rows]
+    E = _lib.DIB_EINVAL
+    rows += [("one pixel", dict(n_pix=1), E, "more than one value per channel is needed to fold an unbiased variance in"),
+             ("a bump without a counter", dict(num_batches_dev=None), E, "bump without num_batches_dev"),
+             ("momentum 1.5", dict(momentum=1.5), E, "momentum above 1 (negative: cumulative average)"),
+             ("momentum NaN", dict(momentum=float("nan")), E, "momentum above 1 (negative: cumulative average)"),
+             ("counter + 4 bytes", dict(num_batches_dev=base["num_batches_dev"] + 4), E, aligned)]
+    check_refusals("dib_bn_acclimate_nhwc", base, tensors, rows)
+    assert tensors["counter"].tolist() == [PRIOR + 1, PRIOR]          # the accepted call at the end: its bump, and nothing beside it
+
+
+def test_the_graph_decision_and_the_layer_agree_on_every_configuration():
+    """C = 8, 3 x 5, no_grad: utils.acclimation_on_device (engine.evaluate: may the trunk be captured?) says yes exactly where the
+    layer takes the HIP path on an input that path accepts.  Every combination of mode, track_running_stats, momentum, counter
+    placement and affine, and three single departures from the plain layer; torch's own error on the torch path counts as torch."""
+    dev = torch.device("cuda")
+    x = _activation(1, 8, 3, 5, dev, 12)
+
+    def noncontiguous_weight(bn):
+        bn.weight = torch.nn.Parameter(torch.ones(16, device=dev)[::2])
+
+    def float64_variance(bn):
+        bn.running_var = bn.running_var.double()
+
+    def switch_off(bn):
+        backbone.FUSE_TEST_TIME_BN = False
+
+    table = [(training, track, momentum, counter, affine, None) for training in (True, False) for track in (True, False)
+             for momentum in (None, 0.1, 1.5) for counter in (("device", "host", None) if track else (None,)) for affine in (True, False)]
+    table += [(True, True, None, "device", True, special) for special in (noncontiguous_weight, float64_variance, switch_off)]
+    seen = set()
+    old = backbone.FUSE_TEST_TIME_BN
+    for training, track, momentum, counter, affine, special in table:
+        what = "training %d, track %d, momentum %s, counter %s, affine %d, %s" % (training, track, momentum, counter, affine,
+                                                                                  special.__name__ if special else "plain")
+        bn = BatchNorm2d(8, momentum=momentum, affine=affine, track_running_stats=track).to(dev).train(training)
+        bn.acclimation_mode = True
+        if track and counter != "device":
+            bn.num_batches_tracked = bn.num_batches_tracked.cpu() if counter == "host" else None
+        try:
+            if special:
+                special(bn)
+            model = torch.nn.Sequential(bn)
+            with torch.no_grad():
+                offered = utils.acclimation_on_device(model, dev)
+                assert utils.acclimation_on_device(model, torch.device("cuda")) == offered, what
+                try:
+                    bn(x)
+                    path = bn.last_path
+                except _lib.DibError:
+                    raise
+                except Exception:
+                    path = "torch"
+        finally:
+            backbone.FUSE_TEST_TIME_BN = old
+        assert offered == (path == "hip") and path in ("hip", "torch"), (what, offered, path)
+        seen.add(path)
+    assert seen == {"hip", "torch"}
 
 
 def test_a_nan_poisons_its_own_channel_only_and_passes_the_relu():

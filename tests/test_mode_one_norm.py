@@ -13,9 +13,6 @@ import copy
 import importlib
 import io
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -327,25 +324,9 @@ def test_unfrozen_batch_norm_stays_refused():
 
 # ---- kernel resources ----------------------------------------------------------------------------------------------------------------
 
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def test_mode_one_kernels_use_no_scratch():
-    if not os.path.isfile(HIPCC):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "detectinblur_amd", "csrc", "dib_bnstats.hip")
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-c", src,
-                        "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    out, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    from tests._kernel_resources import kernel_resources
+    out = kernel_resources("dib_bnstats.hip")
     for frag in ("bn_partial_kernel", "bn_finalize_kernel", "bn_apply_kernel"):
         names = [n for n in out if frag in n]
         assert names, frag

@@ -229,6 +229,70 @@ def test_a_nan_poisons_its_channel_only_and_passes_the_relu():
             assert not bool(torch.isnan(y[:, others]).any())
 
 
+# ---- refusals ------------------------------------------------------------------------------------------------------------------------
+
+# the argument lists of include/dib.h, by name, so that a row of a refusal table names what it changes
+_BN_HEAD = ("x", "residual", "n_pix", "C", "weight", "bias", "running_mean", "running_var", "num_batches_dev")
+_BN_TAIL = ("eps", "relu", "workspace", "workspace_bytes", "stats", "stream")
+BN_ARGUMENTS = {"dib_bn_mode_one_nhwc": _BN_HEAD + ("num_batches",) + _BN_TAIL,
+                "dib_bn_acclimate_nhwc": _BN_HEAD + ("bump", "momentum") + _BN_TAIL}
+NEEDS_SHAPE = "needs n_pix > 0 and C % 4 == 0"
+NULL_POINTER = "null pointer"
+ALIGNED_16 = "x, residual and workspace must be 16-byte aligned"
+
+
+def refusal_case(dev, **own):
+    """A valid call on C = 8, two pixels ([1, 8, 2, 1] channels-last, flat) as a dictionary of arguments, `own` being the entry
+    point's own ones; the tensors behind it -- every buffer four elements longer than the call needs, so that a pointer moved
+    by 4 bytes still points into it -- and the refusals both entry points share: (what, changed arguments, code, fragment)."""
+    from detectinblur_amd import _lib
+    g = torch.Generator().manual_seed(9)
+    C, npix = 8, 2
+    need = _lib.lib().dib_bn_mode_one_workspace_bytes(npix, C)
+    t = {k: torch.randn(n + 4, generator=g).to(dev) for k, n in (("x", C * npix), ("residual", C * npix), ("weight", C), ("bias", C), ("running_mean", C))}
+    t["running_var"] = (torch.rand(C + 4, generator=g) + 0.5).to(dev)
+    t["workspace"] = torch.zeros(need // 4 + 4, dtype=torch.float32, device=dev)
+    t["counter"] = torch.full((2,), N_TRACKED, dtype=torch.int64, device=dev)
+    p = {k: v.data_ptr() for k, v in t.items()}
+    base = dict(x=p["x"], residual=None, n_pix=npix, C=C, weight=p["weight"], bias=p["bias"], running_mean=p["running_mean"],
+                running_var=p["running_var"], num_batches_dev=p["counter"], eps=1e-5, relu=0, workspace=p["workspace"], workspace_bytes=need,
+                stats=None, stream=_lib.stream_of(t["x"]), **own)
+    E = _lib.DIB_EINVAL
+    rows = [("C = 6", dict(C=6), E, NEEDS_SHAPE + " (C = 6)"), ("no pixels", dict(n_pix=0), E, NEEDS_SHAPE + " (C = 8)")]
+    rows += [(k + " null", {k: None}, E, NULL_POINTER) for k in ("x", "running_mean", "running_var", "workspace")]
+    rows += [(k + " + 4 bytes", {k: p[k] + 4}, E, ALIGNED_16) for k in ("x", "residual", "workspace")]
+    rows += [("workspace one byte short", dict(workspace_bytes=need - 1), E, "workspace of %d bytes, needs %d" % (need - 1, need))]
+    return base, t, rows
+
+
+def check_refusals(entry, base, tensors, rows):
+    """Every row is refused with its code and a message that names `entry` and holds the row's fragment, and after a
+    synchronise x, both running buffers and the counter hold the bits they held.  Then the unchanged call is accepted."""
+    from detectinblur_amd import _lib
+    l = _lib.lib()
+    watched = [tensors[k] for k in ("x", "running_mean", "running_var", "counter")]
+    before = [w.clone() for w in watched]
+    for what, change, code, fragment in rows:
+        assert set(change) <= set(base), what
+        args = dict(base, **change)
+        rc = getattr(l, entry)(*[args[k] for k in BN_ARGUMENTS[entry]])
+        text = l.dib_last_error().decode()
+        torch.cuda.synchronize()
+        assert rc == code and text.startswith(entry + ": ") and fragment in text, (what, rc, text)
+        for w, b in zip(watched, before):
+            assert torch.equal(w.view(torch.uint8), b.view(torch.uint8)), what
+    _lib.check(getattr(l, entry)(*[base[k] for k in BN_ARGUMENTS[entry]]))
+    torch.cuda.synchronize()
+
+
+def test_entry_point_refusals_name_their_fault_and_launch_nothing():
+    from detectinblur_amd import _lib
+    base, tensors, rows = refusal_case(torch.device("cuda"), num_batches=N_TRACKED)
+    rows += [("no counter on the device and a negative one on the host", dict(num_batches_dev=None, num_batches=-1), _lib.DIB_EINVAL,
+              "negative num_batches_tracked")]
+    check_refusals("dib_bn_mode_one_nhwc", base, tensors, rows)
+
+
 # ---- the converted detector ----------------------------------------------------------------------------------------------------------
 
 def _detector():
