@@ -704,6 +704,51 @@ int dib_deblur_finish_f16(const void *in_dev, const float *bias_dev, void *out_d
 int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
                       int psf_dtype, int K, int iterations, float eps, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training DeepDeblur's network (`python -m detectinblur_amd.train_deblurrer`, models/deblur_train.py; the reference vendors the
+ * trainer as models/deblur/train.py, dataCommon.py): what runs around MIOpen's convolutions and is not above already.  HBM-bound
+ * streams on `stream`; no allocation, no atomics, no host synchronisation: capturable, and bitwise reproducible from call to call.
+ *
+ * PATCHES.  in_dev: HOST array of B device pointers to planar [3][H[b]][W[b]] images of `dtype` (Half or fp32; sizes may differ);
+ * out_dev: planar [B][3][ps][ps] of the same dtype.  Per image a crop origin (py, px) and a flags word:
+ *     DIB_PATCH_HFLIP | DIB_PATCH_VFLIP | DIB_PATCH_ROT90 | order[0] << 4 | order[1] << 6 | order[2] << 8      (order[c] in 0..2)
+ * in the order of the reference's dataCommon.py (crop :32-39, augment :76-81): the crop, then reverse x, then reverse y, then the
+ * transpose, then out channel c = channel order[c].  Values are moved, never converted: bit-exact.  One launch; B <= 64.
+ * DIB_EINVAL: null / misaligned pointer, unknown dtype, B outside 0..64, ps < 1, unknown flag bits or a channel index of 3.
+ * DIB_ESHAPE: a patch that leaves its image.
+ * ------------------------------------------------------------------------------------- */
+#define DIB_PATCH_HFLIP 1u
+#define DIB_PATCH_VFLIP 2u
+#define DIB_PATCH_ROT90 4u
+int dib_deblur_patches(const void *const *in_dev, int dtype, const int *H, const int *W, const int *py, const int *px,
+                       const unsigned int *flags, int B, int ps, void *out_dev, void *stream);
+
+/* BIAS GRADIENT: the backward pass of dib_bias_act_nhwc / dib_bias_act_mask_nhwc in one pass over a channels-last fp32 gradient
+ * [n_pix][C]:
+ *     grad_out[p][c] = mask bit ? grad_in[p][c] : 0        the mask of dib_bias_act_mask_nhwc; bit-identical to dib_relu_mask_backward;
+ *                                                          grad_out_dev may alias grad_in_dev
+ *     bias_grad[c]   = sum over p of grad_out[p][c]        fp32
+ * mask_dev NULL: no selection (any C >= 1), and grad_out_dev may be NULL too: the plain channel sum.  With a mask C % 4 == 0.
+ * Tensors 16-byte aligned when C % 4 == 0, else 4-byte.  work_dev: dib_bias_grad_workspace_bytes(n_pix, C) bytes.
+ * Two launches: per-slice partial sums into work_dev, then their sum in slice order; the order of every addition depends on
+ * (n_pix, C) alone (csrc/dib_deblur_train.hip states it, with the depth of the tree for error bounds).  A NaN or inf gradient
+ * reaches the sum of its own channel only.  DIB_EINVAL: n_pix or C < 1, n_pix * C > 2^40, null / misaligned pointer, a mask with
+ * C % 4 != 0 or without grad_out_dev. */
+size_t dib_bias_grad_workspace_bytes(long long n_pix, int C);
+int dib_bias_grad_nhwc(const float *grad_in_dev, const unsigned char *mask_dev, float *grad_out_dev, long long n_pix, int C,
+                       float *bias_grad_dev, void *work_dev, void *stream);
+
+/* L1 LOSS of one pyramid level (DeepDeblur's loss, sum over levels of mean |output - target|; its loss/ package is not in the
+ * reference tree: a stated reading).  out_dev: the level's output, channels-last fp32 [n_pix][3]; target_dev: [n_pix][target_stride]
+ * fp32 whose channels 0..2 are read (the layout dib_deblur_pyramid writes: stride 6, coarsest level 3).  With d = out - target:
+ *     grad_dev[p][c] = sign(d) * k,  k = gscale / float(3 n_pix) (one fp32 division)      sign(+-0) = 0; a NaN d gives a NaN (torch.sign gives 0)
+ *     *loss_dev     += (sum of |d|) / float(3 n_pix)                                     summed in a fixed order, as above
+ * The caller zeroes *loss_dev before the first level.  work_dev: dib_l1_pyramid_loss_workspace_bytes(n_pix) bytes.  Two launches.
+ * DIB_EINVAL: n_pix < 1 or > 2^38, target_stride < 3, null / misaligned (4 bytes) pointer. */
+size_t dib_l1_pyramid_loss_workspace_bytes(long long n_pix);
+int dib_l1_pyramid_loss(const float *out_dev, const float *target_dev, int target_stride, long long n_pix, float gscale,
+                        float *grad_dev, float *loss_dev, void *work_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
