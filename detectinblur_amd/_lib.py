@@ -184,6 +184,12 @@ _SIGNATURES = {
     "dib_bias_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
     "dib_bias_grad_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # their Half forms: the trainer under --amp
+    "dib_bias_act_mask_f16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_bias_grad_f16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
+    "dib_bias_grad_f16_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dib_l1_pyramid_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "dib_l1_pyramid_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -17,8 +17,9 @@
 // THE SUMMATION ORDER of (b) and (c) is fixed by the shape alone, so two calls on the same input agree bit for bit:
 //   (b) the [n_pix][C] gradient is cut into S slices of consecutive pixels (bias_grad_geometry below: S = ceil(n_pix / (16 R))
 //       capped at 1024).  A workgroup of 256 lanes takes one slice and QB = min(C / V, 256) lane columns (V = 4 channels per lane
-//       when C % 4 == 0, else 1); lane (row, column) adds the pixels slice_begin + row, + R, + 2 R, ... (R = 256 / QB) one after the
-//       other: a chain of at most L = ceil(slice length / R) additions.  The R rows are then added in LDS as a tree (row r takes row
+//       when C % 4 == 0, else 1; the Half form, dib_bias_grad_f16_nhwc: V = 8 when C % 8 == 0 and the gradient is 16-byte aligned,
+//       else 1 -- one 16-byte load per lane either way, and every Half is exact in fp32, so only the additions below round); lane
+//       (row, column) adds the pixels slice_begin + row, + R, + 2 R, ... (R = 256 / QB) one after the other: a chain of at most L = ceil(slice length / R) additions.  The R rows are then added in LDS as a tree (row r takes row
 //       r + h for h = the powers of two below R, largest first): ceil(log2 R) levels.  The slice's partial sums go to the workspace
 //       [S][C]; the second launch adds them for each channel in slice order, starting from slice 0: S - 1 additions.
 //       DEPTH of the tree, the number of fp32 additions any one input can pass through:  L + ceil(log2 R) + S - 1.
@@ -28,7 +29,7 @@
 //       are added as a tree of 8 levels; the second launch adds the S partial sums in slice order, divides by float(3 n_pix) and adds
 //       the result to the loss scalar.  DEPTH = L + 8 + S - 1 additions, then one division and one addition onto the scalar.
 // models/deblur_train.py restates both geometries (bias_grad_depth, l1_loss_depth) for the tests' error bounds.
-#include "dib_eltwise_vec.h"      // host side: misaligned, launch; F32Lane::select
+#include "dib_eltwise_vec.h"      // host side: misaligned, launch; F32Lane::select, F16Lane::select
 
 namespace dib {
 
@@ -64,18 +65,18 @@ constexpr int BG_THREADS = 256, BG_MAX_SLICES = 1024, BG_PIXELS_PER_LANE = 16;
 
 struct BiasGradGeom {
   long long npix;
-  int C, V;        // channels; channels per lane (4 or 1)
+  int C, V;        // channels; channels per lane (8, 4 or 1)
   int CV, QB, R;   // lane columns in all, per workgroup, pixel rows per workgroup
   int chunks, S;   // workgroups side by side, pixel slices
 };
 
 __host__ __device__ inline long long bg_slice_begin(long long n, int S, int s) { return n / S * s + (n % S < s ? n % S : s); }
 
-static BiasGradGeom bias_grad_geometry(long long npix, int C) {
+static BiasGradGeom bias_grad_geometry(long long npix, int C, int V) {
   BiasGradGeom g;
   g.npix = npix;
   g.C = C;
-  g.V = (C % 4) == 0 ? 4 : 1;
+  g.V = V;
   g.CV = C / g.V;
   g.QB = g.CV < BG_THREADS ? g.CV : BG_THREADS;
   g.R = BG_THREADS / g.QB;
@@ -88,7 +89,17 @@ static BiasGradGeom bias_grad_geometry(long long npix, int C) {
   return g;
 }
 
+// the V fp32 sums of a lane
 template <int V> struct BgVec;
+template <> struct BgVec<8> {
+  typedef f32x8_t T;
+  static __device__ __forceinline__ T zero() { return T{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
+  static __device__ __forceinline__ T add(T a, const T b) { return a + b; }
+  static __device__ __forceinline__ void store(float *p, const T v) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) p[k] = v[k];
+  }
+};
 template <> struct BgVec<4> {
   typedef float4 T;
   static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -104,12 +115,32 @@ template <> struct BgVec<1> {
   static __device__ __forceinline__ void store(float *p, const T v) { p[0] = v; }
 };
 
+// What a lane loads and stores for those V channels, by the gradient's element type E: fp32 -- the sums' own vector -- or IEEE Half, V
+// raw 16-bit words that `up` converts exactly; `select` moves the words and converts nothing.
+template <typename E, int V> struct BgStore;
+template <int V> struct BgStore<float, V> {
+  typedef typename BgVec<V>::T Raw;
+  static __device__ __forceinline__ Raw up(const Raw u) { return u; }
+  static __device__ __forceinline__ Raw select(const Raw u, unsigned m) { return BgVec<V>::select(u, m); }
+};
+template <> struct BgStore<_Float16, 8> {
+  typedef uint4 Raw;
+  static __device__ __forceinline__ f32x8_t up(const Raw u) { return __builtin_convertvector(__builtin_bit_cast(f16x8_t, u), f32x8_t); }
+  static __device__ __forceinline__ Raw select(const Raw u, unsigned m) { return F16Lane::select(u, m); }
+};
+template <> struct BgStore<_Float16, 1> {
+  typedef unsigned short Raw;
+  static __device__ __forceinline__ float up(const Raw u) { return (float)__builtin_bit_cast(_Float16, u); }
+  static __device__ __forceinline__ Raw select(const Raw u, unsigned) { return u; }      // no mask without C % 8 == 0
+};
+
 // grad_in and grad_out may be the same tensor (no __restrict__): a lane reads its vector before it writes it, and no other lane
 // touches that vector.
-template <int V, bool MASK, bool WRITE>
-__global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typename BgVec<V>::T *grad_in, const unsigned char *__restrict__ mask,
-                                                                       typename BgVec<V>::T *grad_out, BiasGradGeom g, float *__restrict__ partial) {
+template <typename E, int V, bool MASK, bool WRITE>
+__global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typename BgStore<E, V>::Raw *grad_in, const unsigned char *__restrict__ mask,
+                                                                       typename BgStore<E, V>::Raw *grad_out, BiasGradGeom g, float *__restrict__ partial) {
   typedef typename BgVec<V>::T T;
+  typedef BgStore<E, V> St;
   __shared__ T sh[BG_THREADS];
   const int t = threadIdx.x;
   const int qi = t % g.QB, row = t / g.QB;
@@ -121,10 +152,10 @@ __global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typ
     const long long p1 = bg_slice_begin(g.npix, g.S, s + 1);
     for (long long p = bg_slice_begin(g.npix, g.S, s) + row; p < p1; p += g.R) {
       const long long i = p * g.CV + q;
-      T v = grad_in[i];
-      if (MASK) v = BgVec<V>::select(v, mask[i]);
+      typename St::Raw v = grad_in[i];
+      if (MASK) v = St::select(v, mask[i]);
       if (WRITE) grad_out[i] = v;
-      acc = BgVec<V>::add(acc, v);
+      acc = BgVec<V>::add(acc, St::up(v));
     }
   }
   sh[t] = acc;
@@ -158,14 +189,14 @@ __global__ __launch_bounds__(BG_THREADS) void bias_grad_final_kernel(const float
   bias_grad[c0 + t] = acc;
 }
 
-template <int V>
-static int bias_grad_run(const float *grad_in, const unsigned char *mask, float *grad_out, const BiasGradGeom &g, float *bias_grad,
+template <typename E, int V>
+static int bias_grad_run(const void *grad_in, const unsigned char *mask, void *grad_out, const BiasGradGeom &g, float *bias_grad,
                          float *work, hipStream_t s) {
-  typedef typename BgVec<V>::T T;
+  typedef typename BgStore<E, V>::Raw Raw;
   const dim3 grid((unsigned)g.S, (unsigned)g.chunks);
-  auto kernel = mask ? bias_grad_partial_kernel<V, true, true>
-                     : grad_out ? bias_grad_partial_kernel<V, false, true> : bias_grad_partial_kernel<V, false, false>;
-  hipLaunchKernelGGL(kernel, grid, dim3(BG_THREADS), 0, s, (const T *)grad_in, mask, (T *)grad_out, g, work);
+  auto kernel = mask ? bias_grad_partial_kernel<E, V, true, true>
+                     : grad_out ? bias_grad_partial_kernel<E, V, false, true> : bias_grad_partial_kernel<E, V, false, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(BG_THREADS), 0, s, (const Raw *)grad_in, mask, (Raw *)grad_out, g, work);
   DIB_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(bias_grad_final_kernel, dim3((unsigned)((g.C + BG_FINAL_CH - 1) / BG_FINAL_CH)), dim3(BG_THREADS), 0, s, (const float *)work,
                      g.S, g.C, bias_grad);
@@ -250,22 +281,53 @@ extern "C" int dib_deblur_patches(const void *const *in_dev, int dtype, const in
 
 extern "C" size_t dib_bias_grad_workspace_bytes(long long n_pix, int C) {
   if (n_pix <= 0 || C <= 0) return 0;
-  return (size_t)bias_grad_geometry(n_pix, C).S * (size_t)C * sizeof(float);
+  return (size_t)bias_grad_geometry(n_pix, C, (C % 4) == 0 ? 4 : 1).S * (size_t)C * sizeof(float);
+}
+
+// Arguments that both element types refuse alike; `lanes`: the channel multiple a mask needs
+static bool bias_grad_args_ok(const char *who, const void *grad_in, const unsigned char *mask, const void *grad_out, long long n_pix, int C,
+                              const float *bias_grad, const void *work, int lanes) {
+  if (n_pix <= 0 || C <= 0 || n_pix > (1ll << 40) / C) { set_error("%s: needs n_pix > 0, C > 0 and n_pix * C <= 2^40", who); return false; }
+  if (C > 65535 * 256) { set_error("%s: C = %d", who, C); return false; }
+  if (!grad_in || !bias_grad || !work) { set_error("%s: null pointer", who); return false; }
+  if (mask && !grad_out) { set_error("%s: a mask without grad_out_dev", who); return false; }
+  if (mask && (C % lanes) != 0) { set_error("%s: a mask needs C %% %d == 0 (C = %d)", who, lanes, C); return false; }
+  return true;
 }
 
 extern "C" int dib_bias_grad_nhwc(const float *grad_in_dev, const unsigned char *mask_dev, float *grad_out_dev, long long n_pix, int C,
                                   float *bias_grad_dev, void *work_dev, void *stream) {
   static const char who[] = "dib_bias_grad_nhwc";
-  if (n_pix <= 0 || C <= 0 || n_pix > (1ll << 40) / C) { set_error("%s: needs n_pix > 0, C > 0 and n_pix * C <= 2^40", who); return DIB_EINVAL; }
-  if (C > 65535 * 256) { set_error("%s: C = %d", who, C); return DIB_EINVAL; }
-  if (!grad_in_dev || !bias_grad_dev || !work_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
-  if (mask_dev && !grad_out_dev) { set_error("%s: a mask without grad_out_dev", who); return DIB_EINVAL; }
-  if (mask_dev && (C % 4) != 0) { set_error("%s: a mask needs C %% 4 == 0 (C = %d)", who, C); return DIB_EINVAL; }
-  const BiasGradGeom g = bias_grad_geometry(n_pix, C);
+  if (!bias_grad_args_ok(who, grad_in_dev, mask_dev, grad_out_dev, n_pix, C, bias_grad_dev, work_dev, 4)) return DIB_EINVAL;
+  const BiasGradGeom g = bias_grad_geometry(n_pix, C, (C % 4) == 0 ? 4 : 1);
   const uintptr_t bits = (uintptr_t)grad_in_dev | (uintptr_t)grad_out_dev | (uintptr_t)bias_grad_dev | (uintptr_t)work_dev;
   if ((bits & (g.V == 4 ? 15 : 3)) != 0) { set_error("%s: tensors must be %d-byte aligned", who, g.V == 4 ? 16 : 4); return DIB_EINVAL; }
-  return g.V == 4 ? bias_grad_run<4>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream)
-                  : bias_grad_run<1>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream);
+  return g.V == 4 ? bias_grad_run<float, 4>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream)
+                  : bias_grad_run<float, 1>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream);
+}
+
+// V = 8 needs 16-byte aligned gradients; anything else takes one channel per lane.  The workspace is sized for that form, whose slices
+// are the shorter ones (R is smaller), so that it serves either.
+static bool bias_grad_f16_wide(const void *grad_in, const void *grad_out, int C) { return (C % 8) == 0 && !misaligned({grad_in, grad_out}); }
+
+extern "C" size_t dib_bias_grad_f16_workspace_bytes(long long n_pix, int C) {
+  if (n_pix <= 0 || C <= 0) return 0;
+  return (size_t)bias_grad_geometry(n_pix, C, 1).S * (size_t)C * sizeof(float);
+}
+
+extern "C" int dib_bias_grad_f16_nhwc(const void *grad_in_dev, const unsigned char *mask_dev, void *grad_out_dev, long long n_pix, int C,
+                                      float *bias_grad_dev, void *work_dev, void *stream) {
+  static const char who[] = "dib_bias_grad_f16_nhwc";
+  if (!bias_grad_args_ok(who, grad_in_dev, mask_dev, grad_out_dev, n_pix, C, bias_grad_dev, work_dev, 8)) return DIB_EINVAL;
+  if ((((uintptr_t)grad_in_dev | (uintptr_t)grad_out_dev) & 1) != 0 || (((uintptr_t)bias_grad_dev | (uintptr_t)work_dev) & 3) != 0) {
+    set_error("%s: tensors must be aligned to their elements", who);
+    return DIB_EINVAL;
+  }
+  const bool wide = bias_grad_f16_wide(grad_in_dev, grad_out_dev, C);
+  if (mask_dev && !wide) { set_error("%s: with a mask the gradients must be 16-byte aligned", who); return DIB_EINVAL; }
+  const BiasGradGeom g = bias_grad_geometry(n_pix, C, wide ? 8 : 1);
+  return wide ? bias_grad_run<_Float16, 8>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream)
+              : bias_grad_run<_Float16, 1>(grad_in_dev, mask_dev, grad_out_dev, g, bias_grad_dev, (float *)work_dev, (hipStream_t)stream);
 }
 
 extern "C" size_t dib_l1_pyramid_loss_workspace_bytes(long long n_pix) {

@@ -1,6 +1,7 @@
-// The one Half entry point of the epilogue family: dib_eltwise_vec.h's bias_act_kernel at 8 Half per lane, behind every convolution of
-// the deblurrer under `--deblur_precision half` (models/deblur.py).  It reproduces torch's Half ops in their order, each computed on
-// upcast values and rounded once: half(y + b), relu(half(y + b)), half(half(y + b) + x).
+// The Half entry points of the epilogue family: dib_eltwise_vec.h's bias_act_kernel at 8 Half per lane, behind every convolution of
+// the deblurrer under `--deblur_precision half` (models/deblur.py) and of its trainer under `--amp` (models/deblur_train.py; there also
+// with the ReLU's sign mask).  It reproduces torch's Half ops in their order, each computed on upcast values and rounded once:
+// half(y + b), relu(half(y + b)), half(half(y + b) + x).
 #include <hip/hip_fp16.h>
 
 #include "dib_eltwise_vec.h"
@@ -36,8 +37,19 @@ extern "C" int dib_bias_act_f16_nhwc(void *x_dev, const float *bias_dev, const v
                                : (relu ? bias_act_f16_scalar_kernel<false, true> : bias_act_f16_scalar_kernel<false, false>);
     return launch(scalar, grid_1d(n_elems), stream, x_dev, bias_dev, residual_dev, n_elems, C);
   }
-  // no sign-mask forms: nothing trains through this graph
+  // the sign-mask forms are dib_bias_act_mask_f16_nhwc's
   auto kernel = residual_dev ? (relu ? bias_act_kernel<F16Lane, true, true, false> : bias_act_kernel<F16Lane, true, false, false>)
                              : (relu ? bias_act_kernel<F16Lane, false, true, false> : bias_act_kernel<F16Lane, false, false, false>);
   return launch(kernel, grid_1d(n_elems / 8), stream, x_dev, bias_dev, residual_dev, n_elems / 8, C / 8, (unsigned char *)nullptr);
+}
+
+// The ReLU form with the sign mask of the STORED values, for the trainer under --amp (models/deblur_train.py): the same kernel, so the
+// same bits as relu = 1 above.  Vector form only: the mask is one byte per 8-element lane vector.
+extern "C" int dib_bias_act_mask_f16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C,
+                                          unsigned char *mask_dev, void *stream) {
+  const char *who = "dib_bias_act_mask_f16_nhwc";
+  if (n_elems < 0 || C <= 0 || (C % 8) != 0 || (n_elems % C) != 0) { set_error("%s: needs C %% 8 == 0 and n_elems a multiple of C", who); return DIB_EINVAL; }
+  int code;
+  if (!args_ok(who, n_elems == 0, {x_dev, bias_dev, mask_dev}, {x_dev, bias_dev, residual_dev}, &code)) return code;
+  return bias_act_launch<F16Lane>(x_dev, bias_dev, residual_dev, n_elems / 8, C / 8, 1, mask_dev, stream);
 }

@@ -5,7 +5,7 @@
 // against the torch expression evaluated in fp32 and cast once (tests/test_detector_ops.py, tests/test_amp_gpu.py).  Pure
 // streaming, HBM-bound; no atomics, no scratch.  dib_eltwise.hip instantiates the fp32 entry points, dib_eltwise_bf16.hip the
 // bf16 ones.  dib_eltwise_f16.hip instantiates ONE member, the bias epilogue, at 8 Half per lane for the deblurrer's Half graph
-// (models/deblur.py), whose ops round one by one: F16Lane::mid is that intermediate rounding.
+// (models/deblur.py; with the sign mask for its trainer's --amp step), whose ops round one by one: F16Lane::mid is that intermediate rounding.
 #pragma once
 #include "dib_common.h"
 #include <initializer_list>
@@ -81,7 +81,8 @@ struct Bf16Lane {
 
 // IEEE Half (the deblurrer under `--deblur_precision half`): 8 per 16-byte vector, converted with the round-to-nearest-even
 // conversions (v_cvt_f16_f32 / v_cvt_f32_f16; NaN stays NaN, what exceeds 65504 after rounding becomes +-inf, denormals are kept).
-// Only what bias_act_kernel reads is here: the other members of the family have no Half form.
+// Only what bias_act_kernel and the trainer's bias_grad_partial_kernel (dib_deblur_train.hip) read is here: the other members of the
+// family have no Half form.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x8_t __attribute__((ext_vector_type(8)));
 
@@ -108,6 +109,8 @@ struct F16Lane {
     for (int k = 0; k < N; ++k) m |= (v[k] > 0.f ? 1u : 0u) << k;
     return m;
   }
+  // the 16-bit words whose mask bit is set, the others +0: no bit of a word is read as a number, so this is the bf16 lane's
+  static __device__ __forceinline__ Raw select(const Raw u, unsigned m) { return Bf16Lane::select(u, m); }
 };
 
 template <class L>

@@ -21,11 +21,25 @@ model.py); `python -m detectinblur_amd.train_deblurrer` is this project's, fed b
                 the bias gradient summed from the same read, in an order fixed by the shape.  PixelShuffle and cat stay torch ops.
               * torch: the plain module, everything else.
             `model.last_path` records which of the two ran ("hip" / "torch").
+            MIXED PRECISION (`--amp`; the reference's train.py:43-46, 97-103): Half levels (`patch_levels(..., torch.float16)`) into
+            the fp32 parameters give Half outputs, again two ways ("hip-amp" / "torch-amp"):
+              * HIP: as above with n_feats % 8 == 0 and FUSE_DEBLUR_TRAIN_AMP.  F.conv2d on Half tensors with `weight.to(float16)` --
+                autograd's own cast, so the master weights get fp32 gradients -- each followed in place by dib_bias_act_f16_nhwc, or
+                dib_bias_act_mask_f16_nhwc for the ReLU, with the fp32 master bias (`_BiasActTrainHalf`); the backward is one
+                dib_bias_grad_f16_nhwc: Half gradient through, fp32 bias gradient.  The 3- and 12-channel convolutions take the
+                scalar epilogue and one channel per lane.  `forward_amp_restated` states its arithmetic in torch ops (tests).
+              * torch: the plain module under torch.autocast(dtype=float16), the reference's.
   loss      `pyramid_l1_loss`: sum over levels of mean |output - target| (DeepDeblur's published L1 loss; its loss/ package is not in
             the reference tree: a stated reading).  On the HIP path one autograd node: dib_l1_pyramid_loss per level adds the level's
             mean into one device scalar and stores the gradient, the backward scales it by the incoming gradient.  The gradient is
             sign(d) / (3 n_pix) with sign(+-0) = 0; a NaN difference gives a NaN gradient there, where torch.sign -- and with it the
             plain path's l1_loss backward -- gives 0: the loss is NaN on both paths, and the driver stops at its next read of it.
+            Under --amp there is no Half loss kernel (three 3-channel outputs are 0.03 % of the step): each Half output goes through
+            `.float()` into this loss, so the loss read is the true, unscaled fp32 loss; GradScaler's `scale(loss).backward()`
+            multiplies the stored sign(d) * k by the scale in fp32 and the cast's backward rounds it to Half once.  The one thing the
+            scaler cannot see: that product, scale / (3 n_pix), has to stay above Half's subnormal range (2^-14 = 6.1e-5) or the
+            gradient of a level loses bits, or all of them, without an inf to skip the step on: 3.3e-4 at the defaults (level 0:
+            n_pix = 16 x 256 x 256) with scale 1024; GradScaler halves the scale on an overflow and never looks below.
 
 Summation orders and the depth of their trees (for error bounds): csrc/dib_deblur_train.hip; restated below as `bias_grad_depth`
 and `l1_loss_depth`."""
@@ -42,6 +56,10 @@ from . import deblur
 # False: the plain module on the GPU too, for A/B runs.  On: 292.0 against 300.7 ms per step at the trainer's defaults on an MI355X,
 # alternated, spread 0.3 % (profiles/deblur_train.txt).
 FUSE_DEBLUR_TRAIN = True
+# The same decision for the Half epilogues under --amp, which run only where FUSE_DEBLUR_TRAIN is on as well; False: the plain module
+# under torch.autocast.  On: 97.2 against 103.1 ms per step at the trainer's defaults, alternated, spread 0.3 %; fp32 in the same run:
+# 289.4 ms (profiles/deblur_train_amp.txt).
+FUSE_DEBLUR_TRAIN_AMP = True
 
 PATCH_HFLIP, PATCH_VFLIP, PATCH_ROT90 = 1, 2, 4          # include/dib.h DIB_PATCH_*
 PATCH_MAX_BATCH = 64                                     # images per dib_deblur_patches launch
@@ -118,22 +136,39 @@ def _level_shape(B, ps, s, n_scales):
     return (B, 6 if s < n_scales - 1 else 3, ps >> s, ps >> s)
 
 
-def patch_levels(patches, n_scales):
+def patch_levels(patches, n_scales, dtype=torch.float32):
     """[B, 3, ps, ps] Half or fp32 in [0, 1] (ps a multiple of 2 ** (n_scales - 1)) -> the levels minus 127.5, finest first, as
-    channels-last fp32 [B, 6, ps >> s, ps >> s] tensors (coarsest [B, 3, ...]) of which channels 0..2 are written."""
+    channels-last fp32 [B, 6, ps >> s, ps >> s] tensors (coarsest [B, 3, ...]) of which channels 0..2 are written.
+    dtype torch.float16 (the inputs under --amp): Half tensors of the same shapes -- dib_deblur_pyramid_f16's half(half(level) - 127.5)
+    on the GPU (the pyramid itself is computed in fp32), the cast of the fp32 levels elsewhere."""
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError("patch_levels: fp32 or Half levels")
     B, ps = int(patches.shape[0]), int(patches.shape[-1])
     if ps % (1 << (n_scales - 1)):
         raise ValueError("patch size %d is not a multiple of %d" % (ps, 1 << (n_scales - 1)))
-    levels = [torch.empty(_level_shape(B, ps, s, n_scales), dtype=torch.float32, device=patches.device, memory_format=torch.channels_last)
+    elem = 2 if dtype == torch.float16 else 4
+    # the pyramid kernels want every slab on 16 bytes: 12 (ps >> s)^2 bytes per fp32 patch at the coarsest level
+    device_ok = patches.is_cuda and 1 <= n_scales <= 4 and all(math.prod(_level_shape(1, ps, s, n_scales)) * elem % 16 == 0 for s in range(n_scales))
+    if dtype == torch.float16 and not device_ok:
+        return [l.to(dtype) for l in patch_levels(patches, n_scales)]
+    levels = [torch.empty(_level_shape(B, ps, s, n_scales), dtype=dtype, device=patches.device, memory_format=torch.channels_last)
               for s in range(n_scales)]
-    # the pyramid kernel wants every slab on 16 bytes: 12 (ps >> s)^2 bytes per patch at the coarsest level
-    if patches.is_cuda and 1 <= n_scales <= 4 and all((l[0].numel() * 4) % 16 == 0 for l in levels):
+    if device_ok:
         from .. import _lib
         patches = patches.contiguous()
-        fn, stream = _lib.lib().dib_deblur_pyramid, _lib.stream_of(patches)
-        dtype = _lib.DIB_F16 if patches.dtype == torch.float16 else _lib.DIB_F32
+        l, stream = _lib.lib(), _lib.stream_of(patches)
+        in_dtype = _lib.DIB_F16 if patches.dtype == torch.float16 else _lib.DIB_F32
+        if dtype == torch.float16:
+            # the fp32 copies of the levels between the finest and the coarsest (include/dib.h): one workspace for all B calls, which
+            # run one after the other on the stream
+            work = torch.empty(sum(3 * (ps >> s) ** 2 for s in range(1, n_scales - 1)), dtype=torch.float32, device=patches.device)
+            work_ptr = work.data_ptr() if work.numel() else None
         for b in range(B):
-            _lib.check(fn(patches[b].data_ptr(), dtype, ps, ps, n_scales, _lib.ptr_array([l[b].data_ptr() for l in levels]), stream))
+            ptrs = _lib.ptr_array([t[b].data_ptr() for t in levels])
+            if dtype == torch.float16:
+                _lib.check(l.dib_deblur_pyramid_f16(patches[b].data_ptr(), in_dtype, ps, ps, n_scales, ptrs, work_ptr, stream))
+            else:
+                _lib.check(l.dib_deblur_pyramid(patches[b].data_ptr(), in_dtype, ps, ps, n_scales, ptrs, stream))
         return levels
     for b in range(B):
         for l, v in zip(levels, deblur.pyramid(deblur.quantise(patches[b]), n_scales)):
@@ -147,9 +182,14 @@ def _ceil_div(a, b):
     return -(-a // b)
 
 
-def bias_grad_depth(n_pix, C):
-    """Additions any one input of dib_bias_grad_nhwc's channel sum can pass through (csrc/dib_deblur_train.hip, "THE SUMMATION ORDER")."""
-    V = 4 if C % 4 == 0 else 1
+def bias_grad_depth(n_pix, C, V=None):
+    """Additions any one input of dib_bias_grad_nhwc's channel sum can pass through (csrc/dib_deblur_train.hip, "THE SUMMATION ORDER").
+    V: channels per lane; None is the fp32 form's (4 when C % 4 == 0, else 1).  dib_bias_grad_f16_nhwc on 16-byte aligned gradients:
+    `bias_grad_lanes(C, torch.float16)`, 8 when C % 8 == 0, else 1."""
+    if V is None:
+        V = 4 if C % 4 == 0 else 1
+    if V not in (1, 4, 8) or C % V:
+        raise ValueError("bias_grad_depth: V = %r with C = %d" % (V, C))
     QB = min(C // V, 256)
     R = 256 // QB
     S = max(1, min(1024, _ceil_div(n_pix, 16 * R)))
@@ -164,18 +204,31 @@ def l1_loss_depth(n_pix):
     return _ceil_div(_ceil_div(n, S), 256) + 8 + S - 1
 
 
+def bias_grad_lanes(C, dtype):
+    """Channels per lane of the bias-gradient kernels on 16-byte aligned gradients; also the elements per mask byte of that dtype."""
+    n = 8 if dtype == torch.float16 else 4
+    return n if C % n == 0 else 1
+
+
 def sign_mask_torch(y):
-    """dib_bias_act_mask_nhwc's mask of a [n_pix, C] (C % 4 == 0) tensor: one byte per 4 consecutive elements, bit k = element > 0."""
-    bits = (y.reshape(-1, 4) > 0).to(torch.uint8)
-    return bits[:, 0] | (bits[:, 1] << 1) | (bits[:, 2] << 2) | (bits[:, 3] << 3)
+    """dib_bias_act_mask_nhwc's mask of a [n_pix, C] (C % 4 == 0) tensor: one byte per 4 consecutive elements, bit k = element > 0.
+    A Half `y` (C % 8 == 0): dib_bias_act_mask_f16_nhwc's, one byte per 8."""
+    n = 8 if y.dtype == torch.float16 else 4
+    bits = (y.reshape(-1, n) > 0).to(torch.uint8)
+    mask = bits[:, 0]
+    for k in range(1, n):
+        mask = mask | (bits[:, k] << k)
+    return mask
 
 
 def bias_grad_torch(grad, mask=None):
-    """dib_bias_grad_nhwc restated: grad [n_pix, C] -> (grad_out, bias_grad)."""
+    """dib_bias_grad_nhwc restated: grad [n_pix, C] -> (grad_out, bias_grad).  A Half `grad`: dib_bias_grad_f16_nhwc, with its mask
+    of one byte per 8 elements, a Half grad_out and the fp32 sum of the upcast values."""
     if mask is not None:
-        bits = ((mask.reshape(-1, 1) >> torch.arange(4, device=mask.device, dtype=torch.uint8)) & 1).reshape(grad.shape).bool()
+        n = 8 if grad.dtype == torch.float16 else 4
+        bits = ((mask.reshape(-1, 1) >> torch.arange(n, device=mask.device, dtype=torch.uint8)) & 1).reshape(grad.shape).bool()
         grad = torch.where(bits, grad, torch.zeros((), dtype=grad.dtype, device=grad.device))
-    return grad, grad.sum(0)
+    return grad, (grad.float() if grad.dtype == torch.float16 else grad).sum(0)
 
 
 def l1_level_torch(out, target, gscale=1.0):
@@ -189,18 +242,38 @@ def l1_level_torch(out, target, gscale=1.0):
 
 def bias_grad_device(grad, mask=None, out=None):
     """dib_bias_grad_nhwc on a channels-last [N, C, H, W] (or a [n_pix, C]) fp32 gradient -> (grad_out, bias_grad); `out` may be
-    `grad` itself; without a mask nothing is written and `grad` is returned as it came."""
+    `grad` itself; without a mask nothing is written and `grad` is returned as it came.  A Half gradient: dib_bias_grad_f16_nhwc
+    (grad_out Half, bias_grad fp32)."""
     from .. import _lib
     C = int(grad.shape[1])
     n_pix = grad.numel() // C
     l = _lib.lib()
+    half = grad.dtype == torch.float16
+    size, run = (l.dib_bias_grad_f16_workspace_bytes, l.dib_bias_grad_f16_nhwc) if half else (l.dib_bias_grad_workspace_bytes, l.dib_bias_grad_nhwc)
     bias_grad = torch.empty(C, dtype=torch.float32, device=grad.device)
-    work = torch.empty(max(1, l.dib_bias_grad_workspace_bytes(n_pix, C) // 4), dtype=torch.float32, device=grad.device)
+    work = torch.empty(max(1, size(n_pix, C) // 4), dtype=torch.float32, device=grad.device)
     if mask is not None and out is None:
         out = torch.empty_like(grad)
-    _lib.check(l.dib_bias_grad_nhwc(grad.data_ptr(), mask.data_ptr() if mask is not None else None, out.data_ptr() if out is not None else None,
-                                    n_pix, C, bias_grad.data_ptr(), work.data_ptr(), _lib.stream_of(grad)))
+    _lib.check(run(grad.data_ptr(), mask.data_ptr() if mask is not None else None, out.data_ptr() if out is not None else None,
+                   n_pix, C, bias_grad.data_ptr(), work.data_ptr(), _lib.stream_of(grad)))
     return (out if out is not None else grad), bias_grad
+
+
+def _bias_act_forward(ctx, x, bias, residual, relu, act, act_mask, lane):
+    """The forward of both epilogue nodes: entry points `act` / `act_mask` (with the ReLU: one mask byte per `lane` elements)."""
+    from .. import _lib
+    C = int(x.shape[1])
+    res = residual.data_ptr() if residual is not None else None
+    ctx.has_res, ctx.masked = residual is not None, bool(relu)
+    l, stream = _lib.lib(), _lib.stream_of(x)
+    if relu:
+        mask = torch.empty(x.numel() // lane, dtype=torch.uint8, device=x.device)
+        _lib.check(getattr(l, act_mask)(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, mask.data_ptr(), stream))
+        ctx.save_for_backward(mask)
+    else:
+        _lib.check(getattr(l, act)(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, 0, stream))
+    ctx.mark_dirty(x)
+    return x
 
 
 class _BiasActTrain(torch.autograd.Function):
@@ -210,19 +283,7 @@ class _BiasActTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, residual, relu):
-        from .. import _lib
-        C = int(x.shape[1])
-        res = residual.data_ptr() if residual is not None else None
-        ctx.has_res, ctx.masked = residual is not None, bool(relu)
-        l, stream = _lib.lib(), _lib.stream_of(x)
-        if relu:
-            mask = torch.empty(x.numel() // 4, dtype=torch.uint8, device=x.device)
-            _lib.check(l.dib_bias_act_mask_nhwc(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, mask.data_ptr(), stream))
-            ctx.save_for_backward(mask)
-        else:
-            _lib.check(l.dib_bias_act_nhwc(x.data_ptr(), bias.data_ptr(), res, x.numel(), C, 0, stream))
-        ctx.mark_dirty(x)
-        return x
+        return _bias_act_forward(ctx, x, bias, residual, relu, "dib_bias_act_nhwc", "dib_bias_act_mask_nhwc", 4)
 
     @staticmethod
     def backward(ctx, grad):
@@ -235,17 +296,35 @@ class _BiasActTrain(torch.autograd.Function):
         return grad, gb, (grad if ctx.has_res else None), None
 
 
+class _BiasActTrainHalf(_BiasActTrain):
+    """Its Half twin (--amp): in place on a channels-last Half CUDA convolution output with the fp32 master bias, which is never
+    rounded to Half -- dib_bias_act_f16_nhwc (8 channels per lane, or its scalar form for the 3- and 12-channel convolutions), or
+    dib_bias_act_mask_f16_nhwc with the ReLU (C % 8 == 0).  The inherited backward is one dib_bias_grad_f16_nhwc: the Half gradient
+    masked bit for bit, the bias gradient summed in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, bias, residual, relu):
+        return _bias_act_forward(ctx, x, bias, residual, relu, "dib_bias_act_f16_nhwc", "dib_bias_act_mask_f16_nhwc", 8)
+
+
 def _bias_act(y, conv, residual=None, relu=False):
-    return _BiasActTrain.apply(y, conv.bias, residual, relu)
+    return (_BiasActTrainHalf if y.dtype == torch.float16 else _BiasActTrain).apply(y, conv.bias, residual, relu)
 
 
 # ---- the network -----------------------------------------------------------------------------------------------------------------
 
-def _hip_ok(model, levels):
+def _hip_ok(model, levels, dtype=torch.float32):
+    """`dtype`: of the levels (the parameters are fp32 either way); Half lanes hold 8 channels."""
     p = next(model.parameters())
-    return (FUSE_DEBLUR_TRAIN and p.is_cuda and p.dtype == torch.float32 and model.n_feats % 4 == 0
-            and all(l.is_cuda and l.device == p.device and l.dtype == torch.float32 and l.dim() == 4 and l.shape[1] in (3, 6)
+    return (FUSE_DEBLUR_TRAIN and (FUSE_DEBLUR_TRAIN_AMP or dtype != torch.float16) and p.is_cuda and p.dtype == torch.float32
+            and model.n_feats % (8 if dtype == torch.float16 else 4) == 0
+            and all(l.is_cuda and l.device == p.device and l.dtype == dtype and l.dim() == 4 and l.shape[1] in (3, 6)
                     and l.is_contiguous(memory_format=torch.channels_last) and l.numel() > 0 for l in levels))
+
+
+def _amp(model, levels):
+    """Half levels into fp32 parameters: the mixed-precision step (--amp)."""
+    return next(model.parameters()).dtype == torch.float32 and len(levels) > 0 and all(l.dtype == torch.float16 for l in levels)
 
 
 def _forward_torch(model, levels):
@@ -258,9 +337,42 @@ def _forward_torch(model, levels):
     return out
 
 
+def _forward_amp_torch(model, levels):
+    """The reference's mixed-precision forward (models/deblur/train.py:97-99): the plain module under autocast."""
+    with torch.autocast(levels[0].device.type, dtype=torch.float16):
+        return _forward_torch(model, levels)
+
+
+def forward_amp_restated(model, levels):
+    """TEST ONLY: the arithmetic of the HIP path under --amp in torch ops on explicit Half tensors -- the same F.conv2d calls, the bias
+    added to the upcast output and rounded once, the ReLU on Half, the residual added to the upcast values and rounded again."""
+    def conv(x, m, residual=None, relu=False):
+        y = F.conv2d(x, m.weight.to(torch.float16), None, 1, m.padding).contiguous(memory_format=torch.channels_last)
+        y = (y.float() + m.bias.view(1, -1, 1, 1)).half()
+        if residual is not None:
+            y = (y.float() + residual.float()).half()
+        return F.relu(y) if relu else y
+
+    n = model.n_scales
+    out, x = [None] * n, levels[-1][:, :3]
+    for s in range(n - 1, -1, -1):
+        body = model.body_models[s].body
+        y = conv(x, body[0])
+        for block in list(body)[1:-1]:
+            y = conv(conv(y, block.body[0], relu=True), block.body[2], residual=y)
+        out[s] = conv(y, body[-1])
+        if s > 0:
+            up = model.conv_end_models[s].uppath[0]
+            x = torch.cat((levels[s - 1][:, :3], F.pixel_shuffle(conv(out[s], up), 2)), 1).contiguous(memory_format=torch.channels_last)
+    return out
+
+
 def _forward_hip(model, levels):
+    half = levels[0].dtype == torch.float16
+
     def conv(x, m):
-        y = F.conv2d(x, m.weight, None, 1, m.padding)
+        # --amp: the cast is autograd's own, so the fp32 master weight gets an fp32 gradient
+        y = F.conv2d(x, m.weight.to(torch.float16) if half else m.weight, None, 1, m.padding)
         return y.contiguous(memory_format=torch.channels_last)            # MIOpen's channels-last kernels give this layout already
 
     n = model.n_scales
@@ -284,7 +396,15 @@ def msresnet_train_forward(model, input_levels):
     (`patch_levels`) -> the list of [B, 3, h, w] outputs of MSResNet before its `+ 127.5`, same order."""
     if len(input_levels) != model.n_scales:
         raise ValueError("%d levels for a network of %d scales" % (len(input_levels), model.n_scales))
-    if _hip_ok(model, input_levels):
+    if _amp(model, input_levels):
+        # Half levels into fp32 parameters (--amp): Half outputs; the caller takes the loss on their `.float()`
+        if _hip_ok(model, input_levels, torch.float16):
+            out = _forward_hip(model, input_levels)
+            model.last_path = "hip-amp"
+        else:
+            out = _forward_amp_torch(model, input_levels)
+            model.last_path = "torch-amp"
+    elif _hip_ok(model, input_levels):
         out = _forward_hip(model, input_levels)
         model.last_path = "hip"
     else:

@@ -13,9 +13,15 @@ Adam.  The host reads the loss only every --print_freq steps: the step itself do
 
 Defaults are DeepDeblur's published ones (-b 16, --patch_size 256, --lr 1e-4, Adam (0.9, 0.999), --lr-steps 500 750 900, --lr-gamma
 0.5, --epochs 1000, 3 scales x 19 blocks x 64 features, 5 x 5 kernels, loss sum_s mean |out_s - target_s|, fp32).  Its option.py and
-loss/ are not in the reference tree: a STATED READING, not pinned.  Not built: the adversarial loss (discriminator.py), Half / amp
+loss/ are not in the reference tree: a STATED READING, not pinned.  Not built: the adversarial loss (discriminator.py), bf16
 training, dataCommon's saturation augmentation and add_noise, a batched pyramid kernel, tuned convolution choices.  No accuracy or
 PSNR claim is made anywhere: synthetic data shows nothing.
+
+--amp (the reference's train.py:43-46, 97-103, deblurInterface.py:144-145): the mixed-precision step.  Half input pyramids and Half
+convolutions on fp32 master weights (models/deblur_train.py, "MIXED PRECISION"), the loss in fp32 on the upcast outputs, against fp32
+targets; `torch.amp.GradScaler(init_scale=--init_scale)` around a FUSED Adam, which takes the scaler's found_inf and scale on the
+device: a step with a non-finite gradient is skipped and the scale halved without the host reading anything.  The printed loss is the
+unscaled one; the scale is read, with the loss, every --print_freq steps.  The checkpoint stays fp32; optim-<N>.pt gains "scaler".
 
 Small images: an image with a side below --patch_size is left out of its step's batch; the count is printed per epoch.
 
@@ -77,6 +83,8 @@ def build_parser():
     p.add_argument("--seed", default=1337, type=int)
     p.add_argument("--save_every", default=10, type=int, help="epochs between checkpoints (the last epoch is always saved)")
     p.add_argument("--validate_images", default=0, type=int, metavar="K")
+    p.add_argument("--amp", action="store_true", help="mixed precision: Half convolutions on fp32 master weights, loss scaling")
+    p.add_argument("--init_scale", default=DEFAULT_INIT_SCALE, type=float, help="--amp: the loss scale GradScaler starts from")
     # the blur: the flags of train.py that the GPU blur reads
     p.add_argument("--gpu_blur", action="store_true", help="implied: the pairs are made by the GPU blur")
     p.add_argument("--cpu_blur", action="store_true", help="refused: the loader's FFT blur would leave no sharp original on the device")
@@ -97,6 +105,17 @@ def build_parser():
     return p
 
 
+DEFAULT_INIT_SCALE = 1024.0      # the reference's (deblurInterface.py:145)
+
+
+def reject_idle_init_scale(args):
+    """--init_scale without --amp would be silently ignored: refuse it."""
+    if not args.amp and args.init_scale != DEFAULT_INIT_SCALE:
+        raise SystemExit("--init_scale %g: the loss scale belongs to --amp, which is not given; drop the flag or add --amp" % args.init_scale)
+    if args.amp and not (math.isfinite(args.init_scale) and args.init_scale > 0):
+        raise SystemExit("--init_scale %g: needs a finite scale above 0" % args.init_scale)
+
+
 def reject(args):
     if args.cpu_blur:
         raise SystemExit("--cpu_blur: the deblurrer trains on pairs made by the GPU blur (the loader's FFT blur hands over no sharp "
@@ -107,6 +126,7 @@ def reject(args):
                          % (args.patch_size, d))
     args.gpu_blur = True
     reject_idle_blur_acc_mode(args)
+    reject_idle_init_scale(args)
     if "coco" not in args.dataset:
         raise SystemExit("--dataset %s: only COCO (and --synthetic) is built" % args.dataset)
 
@@ -177,7 +197,14 @@ class Trainer(object):
         self.net = TrainNet(bare)
         if getattr(args, "distributed", False):
             self.net = torch.nn.parallel.DistributedDataParallel(self.net, device_ids=[args.gpu] if device.type == "cuda" else None)
-        self.optimizer = torch.optim.Adam(bare.parameters(), lr=args.lr, betas=(0.9, 0.999))
+        self.scaler = None
+        if args.amp:
+            # fused: the scaler hands found_inf and the scale to the optimizer's kernel (`_step_supports_amp_scaling`); any other Adam
+            # has the scaler read found_inf on the host every step
+            self.optimizer = torch.optim.Adam(bare.parameters(), lr=args.lr, betas=(0.9, 0.999), fused=True)
+            self.scaler = torch.amp.GradScaler(device.type, init_scale=args.init_scale)
+        else:
+            self.optimizer = torch.optim.Adam(bare.parameters(), lr=args.lr, betas=(0.9, 0.999))
         self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=args.lr_steps, gamma=args.lr_gamma)
         self.jpeg = None
         if args.add_jpeg_artefacts:
@@ -197,12 +224,19 @@ class Trainer(object):
             return None
         blurred, sharp = make_pairs([images_CPU[i] for i in keep], [blur_dicts[i] for i in keep], self.device, self.args, self.jpeg)
         draws = [DT.draw_patch(int(im.shape[-2]), int(im.shape[-1]), ps) for im in sharp]
-        inputs = DT.patch_levels(DT.gather_patches(blurred, draws, ps), self.args.n_scales)
+        amp = self.scaler is not None
+        inputs = DT.patch_levels(DT.gather_patches(blurred, draws, ps), self.args.n_scales, torch.float16 if amp else torch.float32)
         targets = DT.patch_levels(DT.gather_patches(sharp, draws, ps), self.args.n_scales)
-        loss = DT.pyramid_l1_loss(list(self.net(*inputs)), targets)
+        outputs = list(self.net(*inputs))
+        loss = DT.pyramid_l1_loss([o.float() for o in outputs] if amp else outputs, targets)
         self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        if amp:
+            self.scaler.scale(loss).backward()
+            self.scaler.step(self.optimizer)
+            self.scaler.update()
+        else:
+            loss.backward()
+            self.optimizer.step()
         return loss.detach()
 
 
@@ -230,8 +264,10 @@ def save(trainer, args, epoch):
         utils.mkdir(optim_dir)
         warn_if_not_picked(models_dir, epoch)
     utils.save_on_master({"G": trainer.bare.state_dict()}, os.path.join(models_dir, "model-%d.pt" % epoch))
-    utils.save_on_master({"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.scheduler.state_dict(), "epoch": epoch,
-                          "args": vars(args)}, os.path.join(optim_dir, "optim-%d.pt" % epoch))
+    state = {"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.scheduler.state_dict(), "epoch": epoch, "args": vars(args)}
+    if trainer.scaler is not None:
+        state["scaler"] = trainer.scaler.state_dict()
+    utils.save_on_master(state, os.path.join(optim_dir, "optim-%d.pt" % epoch))
 
 
 def resume(trainer, args):
@@ -244,10 +280,17 @@ def resume(trainer, args):
             raise SystemExit("--resume: no optim-<N>.pt under %s" % optim_dir)
         path = os.path.join(optim_dir, "optim-%d.pt" % max(epochs))
     ck = torch.load(path, map_location="cpu", weights_only=False)
+    was_amp = bool(ck.get("args", {}).get("amp", False))
+    if was_amp != bool(args.amp):
+        raise SystemExit("--resume: %s was written %s --amp and this run is %s it: the optimizer state (and the loss scale) of one does "
+                         "not continue the other; %s the flag" % (path, "with" if was_amp else "without", "with" if args.amp else "without",
+                                                                  "add" if was_amp else "drop"))
     model_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "models", "model-%d.pt" % ck["epoch"])
     trainer.bare.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True)["G"], strict=True)
     trainer.optimizer.load_state_dict(ck["optimizer"])
     trainer.scheduler.load_state_dict(ck["lr_scheduler"])
+    if trainer.scaler is not None:
+        trainer.scaler.load_state_dict(ck["scaler"])
     print("Resumed from %s and %s" % (path, model_path))
     return int(ck["epoch"])
 
@@ -333,8 +376,11 @@ def main(argv=None):
             seen += len(images_CPU)
             if loss is not None and it % args.print_freq == 0:
                 value = loss.item()                  # the only read of the step's result: every --print_freq steps
-                print("Epoch: [%d]  [%d/%d]  loss: %.4f  lr: %.6g  path: %s" % (epoch + 1, it, len(loader), value,
-                                                                                 trainer.optimizer.param_groups[0]["lr"], trainer.bare.last_path))
+                line = "Epoch: [%d]  [%d/%d]  loss: %.4f  lr: %.6g  path: %s" % (epoch + 1, it, len(loader), value,
+                                                                                  trainer.optimizer.param_groups[0]["lr"], trainer.bare.last_path)
+                if trainer.scaler is not None:
+                    line += "  scale: %g" % trainer.scaler.get_scale()      # a read of the device, like the loss's: only here
+                print(line)
                 if writer is not None:
                     step = it + epoch * len(loader)
                     writer.add_scalar("losses/l1_pyramid", value, step)

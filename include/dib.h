@@ -447,8 +447,9 @@ int dib_stem_pool_backward_bf16(const void *grad_out_dev, const unsigned short *
 
 /* The IEEE Half form of dib_bias_act_nhwc, the only Half member of the family: the epilogue behind every convolution of the deblurrer
  * under `evaluate.py --deblur_first --deblur_precision half` (below).  x_dev and residual_dev are channels-last Half (raw 16-bit words),
- * bias_dev an fp32 vector holding Half values (the reference's Half biases, upcast).  It reproduces torch's Half ops in their order,
- * each computed on the upcast values and rounded once to nearest even:
+ * bias_dev an fp32 vector of ANY fp32 values: the inference stage passes the reference's Half biases, upcast; the trainer under
+ * `--amp` passes its fp32 master biases, which are never rounded to Half.  It reproduces torch's Half ops in their order, each
+ * computed on the upcast values and rounded once to nearest even:
  *     bias only        x = half(x + b)
  *     bias + ReLU      x = relu(half(x + b))            a NaN stays a NaN, everything else that is not > 0 becomes +0
  *     bias + residual  x = half(half(x + b) + r)        TWO roundings: the reference's ResBlock is `res = body(x); res += x` on Half
@@ -457,6 +458,13 @@ int dib_stem_pool_backward_bf16(const void *grad_out_dev, const unsigned short *
  * are 16-byte aligned; one per lane otherwise, as dib_bias_act_nhwc (the deblurrer's coarser scales end in 3 channels).  n_elems not
  * a multiple of C, null pointers, tensors not aligned to their elements: DIB_EINVAL, nothing launched. */
 int dib_bias_act_f16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C, int relu, void *stream);
+
+/* Its ReLU form with the sign mask, for training (`train_deblurrer.py --amp`): the arithmetic, the roundings and the stored bits of
+ * dib_bias_act_f16_nhwc(..., relu = 1), and mask_dev[n_elems / 8]: one byte per 8 consecutive elements, bit k = STORED element
+ * 8 i + k is > 0 (dib_bias_act_mask_bf16_nhwc's contract; a NaN carries no bit).  Vector form only: C % 8 == 0 and x_dev, bias_dev,
+ * residual_dev 16-byte aligned; anything else, a null x_dev, bias_dev or mask_dev: DIB_EINVAL, nothing launched. */
+int dib_bias_act_mask_f16_nhwc(void *x_dev, const float *bias_dev, const void *residual_dev, long long n_elems, int C,
+                               unsigned char *mask_dev, void *stream);
 
 /* Frozen batch-norm folds of n trunk convolutions in one launch per 32 (torchvision's FrozenBatchNorm2d behind every ResNet
  * convolution, reference models/faster_rcnn.py:367; training re-folds every step because the weights move):
@@ -737,6 +745,19 @@ int dib_deblur_patches(const void *const *in_dev, int dtype, const int *H, const
 size_t dib_bias_grad_workspace_bytes(long long n_pix, int C);
 int dib_bias_grad_nhwc(const float *grad_in_dev, const unsigned char *mask_dev, float *grad_out_dev, long long n_pix, int C,
                        float *bias_grad_dev, void *work_dev, void *stream);
+
+/* The same over a channels-last IEEE Half gradient [n_pix][C] (raw 16-bit words): the backward pass of dib_bias_act_f16_nhwc /
+ * dib_bias_act_mask_f16_nhwc under `train_deblurrer.py --amp`.
+ *     grad_out[p][c] = mask bit ? grad_in[p][c] : +0       the mask of dib_bias_act_mask_f16_nhwc (one byte per 8 elements); the 16
+ *                                                          bits are moved, never converted; grad_out_dev may alias grad_in_dev
+ *     bias_grad[c]   = sum over p of float(grad_out[p][c]) fp32: every Half is exact in fp32, only the additions round
+ * The same kernels, templated over the stored type: the same summation order with 8 channels per lane (one 16-byte load) when
+ * C % 8 == 0 and grad_in_dev / grad_out_dev are 16-byte aligned, else one channel per lane (2-byte aligned).  With a mask C % 8 == 0
+ * and 16-byte alignment.  bias_grad_dev and work_dev: fp32, 4-byte aligned; dib_bias_grad_f16_workspace_bytes(n_pix, C) bytes (the
+ * size of the one-channel-per-lane form, whose slices are the shorter ones: enough for either).  Argument errors as above. */
+size_t dib_bias_grad_f16_workspace_bytes(long long n_pix, int C);
+int dib_bias_grad_f16_nhwc(const void *grad_in_dev, const unsigned char *mask_dev, void *grad_out_dev, long long n_pix, int C,
+                           float *bias_grad_dev, void *work_dev, void *stream);
 
 /* L1 LOSS of one pyramid level (DeepDeblur's loss, sum over levels of mean |output - target|; its loss/ package is not in the
  * reference tree: a stated reading).  out_dev: the level's output, channels-last fp32 [n_pix][3]; target_dev: [n_pix][target_stride]

@@ -4,7 +4,11 @@ is not in the timed window), at the trainer's defaults unless flags say otherwis
 
     python scratch/deblur_train_timing.py ab       FUSE_DEBLUR_TRAIN on / off alternated three times: step time, images/s
     python scratch/deblur_train_timing.py steps    a few fused steps behind a warm-up, to run under `rocprofv3 --kernel-trace --stats`
-    python scratch/deblur_train_timing.py report DIR   sums the *_kernel_stats.csv under DIR by kernel family
+    python scratch/deblur_train_timing.py report DIR   sums the *_kernel_stats.csv under DIR by kernel family; where the per-dispatch
+                                                   *_kernel_trace.csv is there, only the steps behind the warm-up (MIOpen's find, which
+                                                   a fresh process repeats, stays out of the sums)
+    python scratch/deblur_train_timing.py amp      fp32 as shipped / --amp on the HIP path / --amp under autocast, alternated three times
+                                                   (profiles/deblur_train_amp.txt); `steps --amp` is the traced run behind it
 """
 import csv
 import glob
@@ -85,20 +89,93 @@ def ab(extra):
         print("peak device memory %.1f GB" % (torch.cuda.max_memory_allocated() / 2 ** 30))
 
 
+def amp(extra):
+    """Three trainers in one process on the same batches: fp32 as shipped, --amp with the Half HIP epilogues, --amp with the plain module
+    under autocast (FUSE_DEBLUR_TRAIN = False).  The fp32 case is the baseline: the step as it stands without the flag."""
+    from detectinblur_amd.models import deblur_train as DT
+    shipped = DT.FUSE_DEBLUR_TRAIN, DT.FUSE_DEBLUR_TRAIN_AMP
+    cases = (("fp32 as shipped", (), shipped), ("--amp, HIP epilogues", ("--amp",), (True, True)), ("--amp, autocast", ("--amp",), (False, False)))
+    trainers, batches, torch, args = [], None, None, None
+    for name, flags, _ in cases:
+        torch, args, trainer, batches = setup(list(extra) + list(flags))
+        trainers.append(trainer)
+    rounds = int(os.environ.get("DIB_TIMING_STEPS", "6"))
+
+    def select(k):
+        DT.FUSE_DEBLUR_TRAIN, DT.FUSE_DEBLUR_TRAIN_AMP = cases[k][2]
+        return trainers[k]
+
+    times, peaks = [[] for _ in cases], [0.0] * len(cases)
+    for k, (name, _, _) in enumerate(cases):
+        t0 = time.perf_counter()
+        run_steps(torch, select(k), batches, WARM)
+        print("warm-up, %-22s %.1f s for %d steps (path %s)" % (name, time.perf_counter() - t0, WARM, trainers[k].bare.last_path), flush=True)
+    for rep in range(3):
+        for k, (name, _, _) in enumerate(cases):
+            if trainers[k].device.type == "cuda":
+                torch.cuda.reset_peak_memory_stats()
+            dt, loss = run_steps(torch, select(k), batches, rounds)
+            times[k].append(dt)
+            if trainers[k].device.type == "cuda":
+                peaks[k] = max(peaks[k], torch.cuda.max_memory_allocated() / 2 ** 30)
+            scale = trainers[k].scaler.get_scale() if trainers[k].scaler is not None else float("nan")
+            print("round %d  %-22s %.2f ms per step  %.1f images/s  (path %s, last loss %.3f, scale %g)"
+                  % (rep, name, dt * 1e3, args.batch_size / dt, trainers[k].bare.last_path, loss, scale), flush=True)
+    med = [statistics.median(t) for t in times]
+    for k, (name, _, _) in enumerate(cases):
+        t = times[k]
+        print("%-22s median %.2f ms per step (min %.2f, max %.2f; spread %.1f %%)  %.1f images/s  peak memory of its rounds %.1f GB"
+              % (name, med[k] * 1e3, min(t) * 1e3, max(t) * 1e3, 100 * (max(t) - min(t)) / med[k], args.batch_size / med[k], peaks[k]))
+    print("fp32 / amp HIP %.3f x; fp32 / amp autocast %.3f x; amp autocast / amp HIP %.3f x (ratios of medians)"
+          % (med[0] / med[1], med[0] / med[2], med[2] / med[1]))
+    DT.FUSE_DEBLUR_TRAIN, DT.FUSE_DEBLUR_TRAIN_AMP = shipped
+
+
 def steps(extra):
     from detectinblur_amd.models import deblur_train as DT
     torch, args, trainer, batches = setup(extra)
-    DT.FUSE_DEBLUR_TRAIN = True
+    DT.FUSE_DEBLUR_TRAIN = DT.FUSE_DEBLUR_TRAIN_AMP = True
     dt, _ = run_steps(torch, trainer, batches, WARM + TRACED)
     print("%d steps, %.2f ms per step under the tracer (warm-up included)" % (WARM + TRACED, dt * 1e3))
 
 
 FAMILIES = (("(a) patches_kernel", ("patches_kernel",)), ("(b) bias_grad_partial + final", ("bias_grad_",)), ("(c) l1_partial + final", ("l1_partial", "l1_final")),
             ("pyramid launches (deblur_level0 / deblur_down)", ("deblur_level0", "deblur_down")),
-            ("bias_act forward epilogues", ("bias_act_kernel",)), ("the blur (blur_quad / blur_step / compaction)", ("blur_quad", "blur_step", "compact")))
+            ("bias_act forward epilogues", ("bias_act_kernel", "bias_act_f16_scalar")), ("the blur (blur_quad / blur_step / compaction)", ("blur_quad", "blur_step", "compact")))
+
+
+def traced_steps_only(directory):
+    """The per-dispatch trace (*kernel_trace.csv), cut at the first kernel of the first step behind the warm-up (every step begins with
+    the blur's psf_compact launch) and summed by kernel name: the last TRACED steps without whatever MIOpen's find ran in the warm-up.
+    None when the trace is not there or does not hold WARM + TRACED steps."""
+    calls = []
+    for path in glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(path)):
+            calls.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
+    calls.sort()
+    marks = [t0 for t0, _, name in calls if "psf_compact" in name]
+    if len(marks) != WARM + TRACED:
+        return None
+    sums = {}
+    for t0, t1, name in calls:
+        if t0 >= marks[WARM]:
+            c = sums.setdefault(name, [0, 0])
+            c[0] += 1
+            c[1] += t1 - t0
+    return [{"Name": k, "Calls": c, "TotalDurationNs": t, "AverageNs": t / c} for k, (c, t) in sums.items()]
+
+
+DIRECTIONS = (("weight gradients", ("_wrw_", "bwd_weight")), ("data gradients", ("_bwd_", "bwd_data")), ("forward", ("_fwd_", "conv_fwd")))
 
 
 def report(directory):
+    rows = traced_steps_only(directory)
+    if rows is not None:
+        print("from the per-dispatch trace: the %d steps behind the %d warm-up steps" % (TRACED, WARM))
+        searching = sum(int(r["Calls"]) for r in rows if "naive_conv" in r["Name"])
+        if searching:
+            print("WARNING: %d launches of MIOpen's naive reference kernels in the traced steps: its find was still searching" % searching)
+        return summarise(rows, TRACED, "")
     rows = []
     for path in glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
         rows += list(csv.DictReader(open(path)))
@@ -109,10 +186,13 @@ def report(directory):
             rows.append({"Name": name, "Calls": calls, "TotalDurationNs": total, "AverageNs": total / calls})
     if not rows:
         raise SystemExit("no *kernel_stats.csv and no *_results.db under %s" % directory)
-    n = WARM + TRACED
+    summarise(rows, WARM + TRACED, ", the warm-up's among them")
+
+
+def summarise(rows, n, note):
     total = sum(float(r["TotalDurationNs"]) for r in rows)
-    print("all kernels: %.2f ms of device time per step (%d kernels per step; %d steps, the warm-up's among them)"
-          % (total / n / 1e6, sum(int(r["Calls"]) for r in rows) // n, n))
+    print("all kernels: %.2f ms of device time per step (%d kernels per step; %d steps%s)"
+          % (total / n / 1e6, sum(int(r["Calls"]) for r in rows) // n, n, note))
     ours = 0.0
     for title, keys in FAMILIES:
         sel = [r for r in rows if "dib" in r["Name"] and any(k in r["Name"] for k in keys)]
@@ -126,6 +206,13 @@ def report(directory):
                                                                          sum(int(r["Calls"]) for r in torch_side) // n, 100 * tt / total))
     rest = total - ours - tt
     print("  %-50s %9.1f us per step  %27s  %5.2f %%" % ("everything else: MIOpen's convolution kernels", rest / n / 1e3, "", 100 * rest / total))
+    others = [r for r in rows if "dib" not in r["Name"] and "at::native" not in r["Name"]]
+    for title, keys in DIRECTIONS:
+        sel = [r for r in others if any(k in r["Name"] for k in keys)]
+        others = [r for r in others if r not in sel]
+        t = sum(float(r["TotalDurationNs"]) for r in sel)
+        print("    %-48s %9.1f us per step  %5d launches per step  %5.2f %%" % ("of which " + title, t / n / 1e3, sum(int(r["Calls"]) for r in sel) // n,
+                                                                             100 * t / total))
     print("the ten largest:")
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:10]:
         print("  %6.2f %%  %6d calls  %9.1f us each  %s" % (100 * float(r["TotalDurationNs"]) / total, int(r["Calls"]), float(r["AverageNs"]) / 1e3, r["Name"][:110]))
@@ -135,6 +222,8 @@ if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "ab"
     if mode == "ab":
         ab(sys.argv[2:])
+    elif mode == "amp":
+        amp(sys.argv[2:])
     elif mode == "steps":
         steps(sys.argv[2:])
     elif mode == "report":
