@@ -178,6 +178,10 @@ _SIGNATURES = {
     # --deconvolve_first: Richardson-Lucy with the blur's own tap table (models/deconvolve.py)
     "dib_rl_deconvolve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
+    # restoration quality: mse, PSNR and SSIM of one image against another (quality.py)
+    "dib_image_quality_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dib_image_quality": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # the DeepDeblur trainer (models/deblur_train.py): patch gather, epilogue backward with the bias gradient, L1 loss of a level
     "dib_deblur_patches": (ctypes.c_int, [_c_void_pp, ctypes.c_int, _c_int_p, _c_int_p, _c_int_p, _c_int_p, ctypes.POINTER(ctypes.c_uint),
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),

@@ -33,7 +33,7 @@ reseeds the host generators with --seed + epoch, so a resumed run draws what the
 
 --validate_images K: after each saved epoch, K held-out images are blurred with a fixed seed and `Deblurer(output_dir).deblur_` -- the
 shipped inference path, on the checkpoint `find_checkpoint` picks -- is compared with the sharp image: its PSNR beside the PSNR of
-the blurred input, to stdout and TensorBoard.
+the blurred input, and the SSIM of both (quality.py), to stdout and TensorBoard.
 
 On --device cpu (tests, debugging) the network, the patches and the pyramid take their torch paths and the blur is a plain fp32
 torch convolution with the same PSF: a stand-in, not the HIP blur's arithmetic."""
@@ -300,23 +300,37 @@ def psnr(a, b):
     return float("inf") if mse == 0 else 10.0 * math.log10(1.0 / mse)
 
 
+def _planar(image):
+    """what quality.psnr_ssim takes: contiguous, Half or fp32"""
+    image = image if image.dtype in (torch.float16, torch.float32) else image.float()
+    return image if image.is_contiguous() else image.contiguous()
+
+
 @torch.no_grad()
 def validate(dataset, args, device, K):
     """K held-out images blurred with a fixed seed, through the shipped inference path on the directory just written -> (mean PSNR of
-    the deblurred image, mean PSNR of the blurred input), both against the sharp image.  The host generators are left as found."""
+    the deblurred image, mean PSNR of the blurred input, mean SSIM of the deblurred image, mean SSIM of the blurred input, number of
+    images the SSIMs are over: those with both sides of at least 11 pixels), all against the sharp image.  The PSNRs are `psnr`'s; the SSIMs are quality.psnr_ssim's (one HIP pass per pair on a GPU), kept on the device and
+    read once behind the loop.  The host generators are left as found."""
+    from . import quality
     from .models.deblur import Deblurer
     states = random.getstate(), np.random.get_state(), torch.get_rng_state()
     try:
         seed_epoch(args.seed, 10 ** 6)
         deblurer = Deblurer(args.output_dir, device=device)
-        out, inp, n = 0.0, 0.0, 0
+        out, inp, n, ssims = 0.0, 0.0, 0, []
         for i in range(min(K, len(dataset))):
             image, _, bd = dataset[i]
             blurred, sharp = make_pairs([image], [bd], device, args)
-            out += psnr(deblurer.deblur_(blurred[0]), sharp[0])
+            deblurred = deblurer.deblur_(blurred[0])
+            out += psnr(deblurred, sharp[0])
             inp += psnr(blurred[0], sharp[0])
             n += 1
-        return (out / n, inp / n) if n else (float("nan"), float("nan"))
+            if min(sharp[0].shape[-2:]) >= quality.TAPS:      # (a side below the 11-pixel window has no SSIM)
+                ssims.append(torch.stack([quality.psnr_ssim(_planar(deblurred), _planar(sharp[0]))[2],
+                                          quality.psnr_ssim(_planar(blurred[0]), _planar(sharp[0]))[2]]))
+        ssim_out, ssim_inp = torch.stack(ssims).double().mean(0).tolist() if ssims else (float("nan"), float("nan"))
+        return (out / n, inp / n, ssim_out, ssim_inp, len(ssims)) if n else (float("nan"),) * 4 + (0,)
     finally:
         random.setstate(states[0])
         np.random.set_state(states[1])
@@ -396,12 +410,15 @@ def main(argv=None):
         if args.output_dir and ((epoch + 1) % args.save_every == 0 or epoch + 1 == args.epochs):
             save(trainer, args, epoch + 1)
             if dataset_val is not None and utils.is_main_process():
-                out, inp = validate(dataset_val, args, device, args.validate_images)
-                print("Validation: [%d]  PSNR deblurred %.2f dB, blurred input %.2f dB (%d images; no quality claim)"
-                      % (epoch + 1, out, inp, min(args.validate_images, len(dataset_val))))
+                out, inp, ssim_out, ssim_inp, n_ssim = validate(dataset_val, args, device, args.validate_images)
+                print("Validation: [%d]  PSNR deblurred %.2f dB, blurred input %.2f dB; SSIM deblurred %.4f, blurred input %.4f "
+                      "(%d images, SSIM over %d of them; no quality claim)"
+                      % (epoch + 1, out, inp, ssim_out, ssim_inp, min(args.validate_images, len(dataset_val)), n_ssim))
                 if writer is not None:
                     writer.add_scalar("Validation/PSNR_deblurred", out, epoch + 1)
                     writer.add_scalar("Validation/PSNR_blurred_input", inp, epoch + 1)
+                    writer.add_scalar("Validation/SSIM_deblurred", ssim_out, epoch + 1)
+                    writer.add_scalar("Validation/SSIM_blurred_input", ssim_inp, epoch + 1)
             if writer is not None:
                 writer.flush()
     if writer is not None:

@@ -713,6 +713,38 @@ int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_
                       int psf_dtype, int K, int iterations, float eps, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Restoration quality (this library's addition; quality.py, `train_deblurrer.py --validate_images`): how close image a is to image b.
+ * a_dev, b_dev: planar C x H x W, contiguous, each DIB_F16 or DIB_F32 (any pairing), aligned to their element type only; L = data_range.
+ * A stated reading (DeepDeblur reports PSNR and SSIM; its loss/ package is not in the reference tree): Wang et al. 2004 as
+ * skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=L, channel_axis=0).
+ *     mse     = mean over all C H W of (a - b)^2
+ *     psnr_db = 10 log10(L^2 / mse), +inf when mse == 0
+ *     g       : 11 taps, g_k ~ exp(-(k - 5)^2 / (2 1.5^2)), normalised to sum 1, separable
+ *     mu_a, mu_b, E[a a], E[b b], E[a b]: the VALID 11 x 11 correlation with g (x) g: no padding, (H - 10) x (W - 10) windows per channel
+ *     var_a = E[a a] - mu_a^2,  var_b = E[b b] - mu_b^2,  cov = E[a b] - mu_a mu_b;  C1 = (0.01 L)^2,  C2 = (0.03 L)^2
+ *     S       = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2))
+ *     ssim    = mean of S over all windows and channels
+ * out_dev[3] = {mse, psnr_db, ssim}, fp32.
+ * Arithmetic.  Pixels are read as fp32 and shifted by a pivot before the moments; variances and covariance do not depend on a shift
+ * that all pixels of a window share, and the pivot is added back to the means.  WHICH pivot is implementation-defined and not part of
+ * the contract: any per-window-constant shift meets the definition, and results of two implementations agree to rounding, not bit for
+ * bit.  (This one takes the fp32 mean of the pixel tile a workgroup stages, per image: on a flat region that brings the cancellation
+ * error of E[x x] - mu^2 from the order of ulp(L^2 / 4), what a fixed shift by L / 2 leaves, down to the order of ulp(var).)  Moments
+ * (fused multiply-adds, rows left to right, then columns top to bottom) and S in fp32.  The eleven fp32 weights are multiples of 2^-24
+ * that sum to exactly 1 (each within 2.2e-8 of the exact value).  (a - b)^2 is formed from the values as read; a lane adds a handful
+ * of them, and of S, in fp32, everything beyond that is added in fp64: per-workgroup sums go to work_dev, a second small launch adds
+ * those in a fixed order and writes out_dev.  No atomics, no allocation, no host synchronisation: the same bits from run to run of
+ * one build, capturable.  A NaN pixel gives a NaN mse, psnr_db and ssim; nothing traps.  a == b in value gives exactly {0, +inf, 1}.
+ * work_dev: dib_image_quality_workspace_bytes(C, H, W) bytes (0 for a shape the entry refuses), 8-byte aligned; nothing beyond is written.
+ * DIB_EINVAL (nothing launched): null pointer, unknown dtype, C, H or W < 1, L <= 0 or not finite, a misaligned pointer (out_dev: 4
+ * bytes), out_dev or work_dev overlapping an input or each other (a_dev and b_dev may overlap: they are only read).
+ * DIB_ESHAPE: H < 11 or W < 11, or C H W >= 2^31 - 1.
+ * ------------------------------------------------------------------------------------- */
+size_t dib_image_quality_workspace_bytes(int C, int H, int W);
+int dib_image_quality(const void *a_dev, int a_dtype, const void *b_dev, int b_dtype, int C, int H, int W, float data_range,
+                      float *out_dev /* [3]: mse, psnr_db, ssim */, void *work_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training DeepDeblur's network (`python -m detectinblur_amd.train_deblurrer`, models/deblur_train.py; the reference vendors the
  * trainer as models/deblur/train.py, dataCommon.py): what runs around MIOpen's convolutions and is not above already.  HBM-bound
  * streams on `stream`; no allocation, no atomics, no host synchronisation: capturable, and bitwise reproducible from call to call.
