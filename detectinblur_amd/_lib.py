@@ -182,6 +182,11 @@ _SIGNATURES = {
     "dib_image_quality_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dib_image_quality": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ... of one or two candidates against one sharp image, with a per-cell accumulator on the device (quality.RestorationMeter)
+    "dib_restoration_quality_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dib_restoration_quality": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_void_pp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
     # the DeepDeblur trainer (models/deblur_train.py): patch gather, epilogue backward with the bias gradient, L1 loss of a level
     "dib_deblur_patches": (ctypes.c_int, [_c_void_pp, ctypes.c_int, _c_int_p, _c_int_p, _c_int_p, _c_int_p, ctypes.POINTER(ctypes.c_uint),
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),

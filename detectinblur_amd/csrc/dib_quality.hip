@@ -31,203 +31,76 @@
 // to exactly 1 in fp32 IN ANY ORDER (every partial sum is a multiple of 2^-24 below 1): a constant image has exactly constant means
 // (for a constant whose products with 2^-24 are exact) and exactly zero variance.  |g_k - exact| <= 2.2e-8, the
 // order of the fp32 rounding of the weights themselves.
-#include <hip/hip_fp16.h>
-
-#include <math.h>
-
-#include "dib_common.h"
+// The phases themselves are in dib_quality_dev.h: dib_restoration.hip (one sharp image against one or two candidates in one launch)
+// promises this file's bits for every candidate and calls the same functions.
+#include "dib_quality_dev.h"
 
 namespace dib {
 namespace {
 
-constexpr int Q_TW = 32, Q_TH = 32, Q_TAPS = 11, Q_HALO = Q_TAPS - 1;
-constexpr int Q_IW = Q_TW + Q_HALO, Q_IH = Q_TH + Q_HALO;                 // 42 x 42 pixels per image
-constexpr int Q_PIX = Q_IW * Q_IH, Q_ROWSUMS = Q_IH * Q_TW;               // 1,764 pixels; 1,344 row sums per plane
-constexpr int Q_THREADS = 256, Q_STAGE_TRIPS = (Q_PIX + Q_THREADS - 1) / Q_THREADS, Q_ROW_TRIPS = (Q_ROWSUMS + Q_THREADS - 1) / Q_THREADS;
-constexpr int Q_LANE_ROWS = Q_TH * Q_TW / Q_THREADS;                      // 4 windows per lane
 constexpr int Q_LDS_WORDS = 5 * Q_ROWSUMS;
 static_assert(2 * Q_PIX <= Q_LDS_WORDS, "the five planes of row sums overwrite the two pixel tiles");
-static_assert(Q_TW == 32 && Q_THREADS / Q_TW * Q_LANE_ROWS == Q_TH, "a half-wave is one tile row wide; eight of them, four rows each");
-
-__device__ __forceinline__ float q_weight(int k) {
-  constexpr float G[Q_TAPS] = {17253.f / 16777216.f,   127486.f / 16777216.f,  603993.f / 16777216.f, 1834768.f / 16777216.f,
-                               3573640.f / 16777216.f, 4462936.f / 16777216.f, 3573640.f / 16777216.f, 1834768.f / 16777216.f,
-                               603993.f / 16777216.f,  127486.f / 16777216.f,  17253.f / 16777216.f};
-  return G[k];
-}
-
-__device__ __forceinline__ float q_load(const float *p, size_t i) { return p[i]; }
-__device__ __forceinline__ float q_load(const __half *p, size_t i) { return __half2float(p[i]); }
-
-// sum over the wave's 64 lanes, the same order on every lane (xor butterfly): all lanes end with the same value
-template <typename T>
-__device__ __forceinline__ T q_wave_sum(T v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+// the window as stated above, against the shared table
+static_assert(Q_G[0] == 17253.f / 16777216.f && Q_G[1] == 127486.f / 16777216.f && Q_G[2] == 603993.f / 16777216.f &&
+                  Q_G[3] == 1834768.f / 16777216.f && Q_G[4] == 3573640.f / 16777216.f && Q_G[5] == 4462936.f / 16777216.f &&
+                  Q_G[6] == Q_G[4] && Q_G[7] == Q_G[3] && Q_G[8] == Q_G[2] && Q_G[9] == Q_G[1] && Q_G[10] == Q_G[0],
+              "round(2^24 g_k) / 2^24, symmetric");
 
 // grid = tiles_x * tiles_y * C workgroups, flat (a plane's tiles row by row); work: two doubles per workgroup
 template <typename TA, typename TB>
 __global__ __launch_bounds__(Q_THREADS, 4) void quality_tile_kernel(const TA *__restrict__ a, const TB *__restrict__ b, int H, int W, int tiles_x,
                                                                     int tiles_y, float c1, float c2, double *__restrict__ work) {
   __shared__ float lds[Q_LDS_WORDS];
-  __shared__ double red[2 * Q_THREADS / 64];
-  __shared__ float piv[2 * Q_THREADS / 64];
+  __shared__ double red[2 * Q_WAVES];
+  __shared__ float piv[2 * Q_WAVES];
   const int tid = threadIdx.x;
-  const int per_plane = tiles_x * tiles_y;
-  const int plane_id = blockIdx.x / per_plane, t = blockIdx.x - plane_id * per_plane;
-  const int ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int x0 = tx * Q_TW, y0 = ty * Q_TH;
-  const bool last_col = tx == tiles_x - 1, last_row = ty == tiles_y - 1;
-  const size_t plane = (size_t)plane_id * H * W;
+  const QTile q = q_tile(H, W, tiles_x, tiles_y);
   float *pa = lds, *pb = lds + Q_PIX;
-  float sq = 0.f, ss = 0.f;
 
   // 1. the two pixel tiles; the squared differences of the pixels this workgroup owns; each tile's mean as its pivot
-  float va[Q_STAGE_TRIPS], vb[Q_STAGE_TRIPS];
-  float suma = 0.f, sumb = 0.f;
-#pragma unroll
-  for (int it = 0; it < Q_STAGE_TRIPS; ++it) {
-    const int p = tid + it * Q_THREADS;
-    va[it] = vb[it] = 0.f;
-    if (p < Q_PIX) {
-      const int r = p / Q_IW, c = p - r * Q_IW;
-      const int gy = y0 + r, gx = x0 + c;
-      const size_t e = plane + (size_t)min(gy, H - 1) * W + min(gx, W - 1);
-      va[it] = q_load(a, e);
-      vb[it] = q_load(b, e);
-      const float d = va[it] - vb[it];
-      const bool owned = gy < H && gx < W && (c < Q_TW || last_col) && (r < Q_TH || last_row);
-      sq += owned ? d * d : 0.f;
-      suma += va[it];
-      sumb += vb[it];
-    }
-  }
-  suma = q_wave_sum(suma);
-  sumb = q_wave_sum(sumb);
+  QStaged s;
+  q_stage_read<false>(a, b, b, q, false, s);
+  const float sq = s.sq_a;
+  const float suma = q_wave_sum(s.sum_a), sumb = q_wave_sum(s.sum_b);
   if ((tid & 63) == 0) {
     piv[2 * (tid >> 6)] = suma;
     piv[2 * (tid >> 6) + 1] = sumb;
   }
   __syncthreads();
-  const float pivot_a = (((piv[0] + piv[2]) + piv[4]) + piv[6]) / (float)Q_PIX, pivot_b = (((piv[1] + piv[3]) + piv[5]) + piv[7]) / (float)Q_PIX;
-#pragma unroll
-  for (int it = 0; it < Q_STAGE_TRIPS; ++it) {
-    const int p = tid + it * Q_THREADS;
-    if (p < Q_PIX) {
-      pa[p] = va[it] - pivot_a;
-      pb[p] = vb[it] - pivot_b;
-    }
-  }
+  const float pivot_a = q_pivot(piv, 0, 2), pivot_b = q_pivot(piv, 1, 2);
+  q_stage_write(pa, s.va, pivot_a);
+  q_stage_write(pb, s.vb, pivot_b);
   __syncthreads();
 
   // 2. the row sums of the five quantities, in registers until the pixel tiles are no longer read
   float h[Q_ROW_TRIPS][5];
-#pragma unroll
-  for (int it = 0; it < Q_ROW_TRIPS; ++it) {
-    const int item = min(tid + it * Q_THREADS, Q_ROWSUMS - 1);      // (the last trip's idle lanes redo the last item and drop it)
-    const int r = item >> 5, x = item & 31;
-    const float *ra = pa + r * Q_IW + x, *rb = pb + r * Q_IW + x;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
-#pragma unroll
-    for (int k = 0; k < Q_TAPS; ++k) {
-      const float g = q_weight(k), xa = ra[k], xb = rb[k];
-      s0 = __builtin_fmaf(g, xa, s0);
-      s1 = __builtin_fmaf(g, xb, s1);
-      s2 = __builtin_fmaf(g, xa * xa, s2);
-      s3 = __builtin_fmaf(g, xb * xb, s3);
-      s4 = __builtin_fmaf(g, xa * xb, s4);
-    }
-    h[it][0] = s0; h[it][1] = s1; h[it][2] = s2; h[it][3] = s3; h[it][4] = s4;
-  }
+  q_row_sums<true>(pa, pb, h);
   __syncthreads();
 #pragma unroll
-  for (int it = 0; it < Q_ROW_TRIPS; ++it) {
-    const int item = tid + it * Q_THREADS;
-    if (item < Q_ROWSUMS) {
-#pragma unroll
-      for (int q = 0; q < 5; ++q) lds[q * Q_ROWSUMS + item] = h[it][q];
-    }
-  }
+  for (int p = 0; p < 5; ++p) q_row_write(lds + p * Q_ROWSUMS, h, p);
   __syncthreads();
 
   // 3. the column sums of this lane's four windows, and S
-  const int x = tid & 31, yg = (tid >> 5) * Q_LANE_ROWS;
-  float m[5][Q_LANE_ROWS];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    float col[Q_LANE_ROWS + Q_HALO];
-#pragma unroll
-    for (int r = 0; r < Q_LANE_ROWS + Q_HALO; ++r) col[r] = lds[q * Q_ROWSUMS + (yg + r) * Q_TW + x];
-#pragma unroll
-    for (int j = 0; j < Q_LANE_ROWS; ++j) {
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < Q_TAPS; ++k) s = __builtin_fmaf(q_weight(k), col[j + k], s);
-      m[q][j] = s;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < Q_LANE_ROWS; ++j) {
-    const float ma = m[0][j], mb = m[1][j];                       // the means of the shifted images
-    const float var_a = m[2][j] - ma * ma, var_b = m[3][j] - mb * mb, cab = m[4][j] - ma * mb;
-    const float mua = ma + pivot_a, mub = mb + pivot_b;
-    const float num = (2.f * (mua * mub) + c1) * (2.f * cab + c2);
-    const float den = (mua * mua + mub * mub + c1) * (var_a + var_b + c2);
-    const float S = num / den;
-    const bool exists = x0 + x < W - Q_HALO && y0 + yg + j < H - Q_HALO;
-    ss += exists ? S : 0.f;
-  }
+  const float ss = q_window_sum(lds, lds + Q_ROWSUMS, lds + 2 * Q_ROWSUMS, lds + 3 * Q_ROWSUMS, lds + 4 * Q_ROWSUMS, q, pivot_a, pivot_b, c1, c2);
 
   // 4. the workgroup's two sums, in fp64
-  const double ws = q_wave_sum((double)ss), wq = q_wave_sum((double)sq);
-  if ((tid & 63) == 0) {
-    red[2 * (tid >> 6)] = ws;
-    red[2 * (tid >> 6) + 1] = wq;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    work[2 * (size_t)blockIdx.x] = ((red[0] + red[2]) + red[4]) + red[6];
-    work[2 * (size_t)blockIdx.x + 1] = ((red[1] + red[3]) + red[5]) + red[7];
-  }
+  q_group_sums(ss, sq, red, work + 2 * (size_t)blockIdx.x);
 }
 
 // one workgroup: lane l adds workgroups l, l + 256, ... in that order, then a fixed tree over the 256 lanes
 __global__ __launch_bounds__(Q_THREADS) void quality_finish_kernel(const double *__restrict__ work, int n_groups, double n_pixels, double n_windows,
                                                                    double range, float *__restrict__ out) {
   __shared__ double rs[Q_THREADS], rq[Q_THREADS];
-  const int tid = threadIdx.x;
-  double s = 0.0, q = 0.0;
-  for (int i = tid; i < n_groups; i += Q_THREADS) {
-    s += work[2 * (size_t)i];
-    q += work[2 * (size_t)i + 1];
-  }
-  rs[tid] = s;
-  rq[tid] = q;
-  __syncthreads();
-  for (int w = Q_THREADS / 2; w >= 1; w >>= 1) {
-    if (tid < w) {
-      rs[tid] += rs[tid + w];
-      rq[tid] += rq[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const double mse = rq[0] / n_pixels;
-    out[0] = (float)mse;
-    out[1] = mse == 0.0 ? INFINITY : (float)(10.0 * log10(range * range / mse));      // a NaN mse compares unequal: NaN
-    out[2] = (float)(rs[0] / n_windows);
-  }
+  q_final_sums(work, n_groups, 2, rs, rq);
+  if (threadIdx.x == 0) q_figures(rs[0], rq[0], n_pixels, n_windows, range, out);
 }
 
 template <typename TA, typename TB>
 int quality_launch(const void *a, const void *b, int C, int H, int W, float range, float *out, double *work, hipStream_t s) {
-  const int tiles_x = (W - Q_HALO + Q_TW - 1) / Q_TW, tiles_y = (H - Q_HALO + Q_TH - 1) / Q_TH;
+  const int tiles_x = q_tiles(W), tiles_y = q_tiles(H);
   const int groups = tiles_x * tiles_y * C;
-  const float c1 = (0.01f * range) * (0.01f * range), c2 = (0.03f * range) * (0.03f * range);
   hipLaunchKernelGGL((quality_tile_kernel<TA, TB>), dim3(groups), dim3(Q_THREADS), 0, s, (const TA *)a, (const TB *)b, H, W, tiles_x, tiles_y,
-                     c1, c2, work);
+                     q_c1(range), q_c2(range), work);
   DIB_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(quality_finish_kernel, dim3(1), dim3(Q_THREADS), 0, s, (const double *)work, groups, (double)C * H * W,
                      (double)C * (H - Q_HALO) * (W - Q_HALO), (double)range, out);
@@ -235,18 +108,12 @@ int quality_launch(const void *a, const void *b, int C, int H, int W, float rang
   return DIB_OK;
 }
 
-// workgroups of the tile kernel (0 where the entry point refuses the shape): C H W < 2^31 bounds it
-long long quality_groups(int C, int H, int W) {
-  if (C < 1 || H < Q_TAPS || W < Q_TAPS || (long long)C * H * W >= 0x7fffffffll) return 0;
-  return (long long)C * ((H - Q_HALO + Q_TH - 1) / Q_TH) * ((W - Q_HALO + Q_TW - 1) / Q_TW);
-}
-
 }  // namespace
 }  // namespace dib
 
 using namespace dib;
 
-extern "C" size_t dib_image_quality_workspace_bytes(int C, int H, int W) { return (size_t)quality_groups(C, H, W) * 2 * sizeof(double); }
+extern "C" size_t dib_image_quality_workspace_bytes(int C, int H, int W) { return (size_t)q_groups(C, H, W) * 2 * sizeof(double); }
 
 extern "C" int dib_image_quality(const void *a_dev, int a_dtype, const void *b_dev, int b_dtype, int C, int H, int W, float data_range,
                                  float *out_dev, void *work_dev, void *stream) {

@@ -462,7 +462,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
              gpu_blur=False, expand_target_boxes=False, deblur_first=False, deblurer=None, use_custom_image_norm=False,
              use_ensemble=False, ensemble_models=None, blur_estimator=None, add_noise=False, noise_level=0.001, add_block=False,
              add_jpeg_artifact=False, image_output_folder=None, LEHE=False, epoch_number=None, blur_acc_mode="bitexact",
-             deconvolve_first=False, deconvolver=None):
+             deconvolve_first=False, deconvolver=None, restoration_metrics=False, restoration_quantize8=False):
     """reference engine.py:220-416.  Runs the detector (or the routed ensemble) over the loader, scores the
     detections against the dataset's COCO ground truth (boxes replaced by the expanded ones under
     `expand_target_boxes`, :325-342) and returns the evaluator (see EvaluationResult).
@@ -474,6 +474,10 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     batch -- when its blur_dict says it was blurred -- is replaced by `deconvolver.deconvolve_(image, blur_dict, psf, tables)`
     (models/deconvolve.py: Richardson-Lucy with the image's own PSF, the tap table the blur has just read; fp32 out).  The ground truth
     grown by `expand_target_boxes` stays the blurred image's.
+    `restoration_metrics` (this repo, --restoration_metrics): in a pass that blurs on the device, PSNR and SSIM of the blurred first image
+    of every batch and of what `deblur_first` / `deconvolve_first` makes of it, against that image before the blur, accumulated on the
+    device (quality.RestorationMeter; `restoration_quantize8`: on 8-bit grey levels) and read once behind the loop: the result gains
+    the key "restoration".  Off: nothing is allocated, nothing launched, no key.
     A model that evaluate.py marked for online batch-norm statistics (`acclimate_norm`, with `acclimation_carry_over`): after eval() its
     batch-norm layers go back into training mode (utils.turn_batch_norm_on) and, unless the statistics carry over, the pass starts
     from the snapshot (utils.restore_BN_stats_from_old, in place).  The graphed trunk and the pipelined loop carry the state: the
@@ -496,6 +500,11 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         raise ValueError("evaluate(deconvolve_first=True) needs a deconvolver (models.deconvolve.Deconvolver)")
     if deconvolving and deblurring:
         raise ValueError("evaluate: deblur_first and deconvolve_first both replace the image in front of the detector; choose one")
+    meter = None
+    if restoration_metrics and gpu_blur and blurring_images:
+        from .quality import RestorationMeter
+        meter = RestorationMeter(device, quantize8=restoration_quantize8,
+                                 names=("blurred", "restored") if (deblurring or deconvolving) else ("blurred",))
     jpeg_compressor = None
     if add_jpeg_artifact:                                                # reference :248-254
         from .models.jpeg import DiffJPEG
@@ -585,12 +594,22 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         def prepare(batch, staged):
             images_CPU, targets_CPU, blur_dicts = batch
             images_GPU, targets_GPU, psfs_GPU, thetas, l1, l2, tables = staged
+            # --restoration_metrics: image 0 as it stands BEFORE the blur (one copy on this stream), the blurred image the detector or
+            # the stage gets, and what the stage makes of it; quality.RestorationMeter queues two launches behind the stage on this
+            # stream and reads nothing, so the look-ahead, the graphed trunk and the pictures are untouched.  `blur_image_list` replaces
+            # the list ENTRY and today's blur paths write a fresh tensor, so a reference would give the same figures; the copy (6.4 MB
+            # at full size) keeps the sharp image independent of how a blur path treats its input
+            measured = meter is not None and gpu_blur and blurring_images and bool(blur_dicts[0]["blurring"])
+            if meter is not None and not measured:
+                meter.skip()
+            sharp = images_GPU[0].clone() if measured else None
             if gpu_blur and blurring_images:
                 blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, add_noise=add_noise, noise_level=noise_level,
                                                add_block=add_block, add_jpeg_artifact=add_jpeg_artifact,
                                                jpeg_compressor=jpeg_compressor, acc_mode=acc_mode, tables=tables)
             if expand_target_boxes and blurring_images:
                 targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
+            blurred = images_GPU[0]      # a handle, no copy: a stage has to hand back a new tensor (checked below)
             if deblurring:
                 # reference :319-322, the FIRST image only (batch size 1 in every driver).  On a GPU the image stays there: three HIP
                 # kernels and MIOpen's convolutions on the current stream, no synchronisation (models/deblur.py).  The result is
@@ -602,6 +621,15 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 # tables hold the blurring PSFs in batch order, so image 0's table is table 0; without staged tables (the CPU, mixed
                 # canvases) the stage compacts the PSF itself.  fp32 out, like the deblurrer's.
                 images_GPU[0] = deconvolver.deconvolve_(images_GPU[0], blur_dicts[0], psfs_GPU[0], tables, 0)
+            if measured:
+                restored = images_GPU[0] if (deblurring or deconvolving) else None
+                if restored is not None and (restored is blurred or restored.data_ptr() == blurred.data_ptr()):
+                    raise RuntimeError("evaluate(restoration_metrics=True): the stage handed back the tensor it was given; the blurred "
+                                       "image it would be compared with is gone (copy it before a stage that works in place)")
+                if restored is not None and restored.shape != sharp.shape:
+                    raise RuntimeError("evaluate(restoration_metrics=True): the stage was given an image of %s and returned %s"
+                                       % (tuple(sharp.shape), tuple(restored.shape)))
+                meter.update(sharp, blurred, restored)      # Half from the blur, fp32 from the stages: the kernel takes the mix as it is
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
             est = None
             if use_ensemble and blur_estimator is not None:                  # reference :354-366 (the routing itself: below)
@@ -742,10 +770,15 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         f.result()                                                       # re-raises anything the scoring thread hit
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
+    extra = {}
+    if meter is not None:
+        from .quality import format_restoration
+        extra["restoration"] = meter.result()                            # one device read; a collective on every rank, like the evaluator's
+        print(format_restoration(extra["restoration"]))
     print("Number of Faulty boxes: " + str(faulty_boxes) + " Total number of boxes: " + str(total_boxes))
     coco_evaluator.synchronize_between_processes()                       # a collective on every rank, shards empty or not
     coco_evaluator.accumulate()
     stats = coco_evaluator.summarize() if utils.is_main_process() else coco_evaluator.coco_eval["bbox"].summarize()
     has_gt = len(coco_evaluator.coco_gt.dataset.get("annotations", [])) > 0
     return EvaluationResult(coco_evaluator, detections=detections, targets=gt_boxes, routes=routes, meters=metric_logger,
-                            coco_stats=stats if has_gt else None)
+                            coco_stats=stats if has_gt else None, **extra)

@@ -72,6 +72,11 @@ def build_parser():
     p.add_argument("--deconvolve_iterations", type=int, default=DECONVOLVE_ITERATIONS, metavar="N", action=_StoreGiven, help="(this repo) with --deconvolve_first: "
                    "Richardson-Lucy iterations, 1..%d (default %d); more sharpen further and amplify noise and JPEG residue further"
                    % (MAX_DECONVOLVE_ITERATIONS, DECONVOLVE_ITERATIONS))
+    p.add_argument("--restoration_metrics", action="store_true", help="(this repo) Per sweep cell, PSNR and SSIM of the blurred image and "
+                   "of what --deblur_first / --deconvolve_first makes of it, against the image before the blur (quality.py; one HIP pass "
+                   "per image, accumulated on the device).  Needs --gpu_blur.  No accuracy claim")
+    p.add_argument("--restoration_8bit", action="store_true", help="(this repo) with --restoration_metrics: score the images as their "
+                   "8-bit grey levels (data range 255), as figures computed from saved pictures are")
     return p
 
 
@@ -102,6 +107,20 @@ def reject_deconvolution_conflicts(args):
                          "that forward model")
     if not (1 <= n <= MAX_DECONVOLVE_ITERATIONS):
         raise SystemExit("--deconvolve_iterations %d: the iteration count lies in 1..%d" % (n, MAX_DECONVOLVE_ITERATIONS))
+
+
+def reject_restoration_metrics_conflicts(args):
+    """--restoration_metrics' refusals, before anything is built."""
+    if not getattr(args, "restoration_metrics", False):
+        if getattr(args, "restoration_8bit", False):
+            raise SystemExit("--restoration_8bit needs --restoration_metrics: it sets how those figures are computed and nothing else reads it")
+        return
+    if getattr(args, "vanilla_eval", False):
+        raise SystemExit("--restoration_metrics with --vanilla_eval: the clean pass blurs nothing, there is no image to compare with the "
+                         "sharp one")
+    if getattr(args, "cpu_blur", False) or not getattr(args, "gpu_blur", False):
+        raise SystemExit("--restoration_metrics needs --gpu_blur (and not --cpu_blur): the sharp image is kept where the blur runs, right "
+                         "before the blur replaces it; --cpu_blur blurs in the loaders' transform and hands the driver no sharp image")
 
 
 def build_deconvolver(args):
@@ -159,6 +178,7 @@ def main(args):
     reject_out_of_scope(args)
     reject_acclimation_conflicts(args)
     reject_deconvolution_conflicts(args)
+    reject_restoration_metrics_conflicts(args)
     if getattr(args, "deblur_first", False) and not getattr(args, "deblurer_model_location", None):
         raise SystemExit("--deblur_first needs --deblurer_model_location: a DeepDeblur experiment directory (models/model-<N>.pt) or a "
                          "checkpoint file; the reference's default is a path on its author's disk and nothing is downloaded "
@@ -225,6 +245,9 @@ def main(args):
     deblur_kw = dict(deblur_first=bool(getattr(args, "deblur_first", False)), deblurer=deblurer)
     deconvolver = build_deconvolver(args)
     deconvolve_kw = dict(deconvolve_first=deconvolver is not None, deconvolver=deconvolver)
+    metrics_kw = {}
+    if getattr(args, "restoration_metrics", False):      # (off: engine.evaluate is called exactly as before)
+        metrics_kw = dict(restoration_metrics=True, restoration_quantize8=bool(getattr(args, "restoration_8bit", False)))
 
     def loader_for(tf):
         ds, _ = get_coco(args.data_path, "val", tf, synthetic=synthetic, with_masks=getattr(args, "with_masks", False))
@@ -260,11 +283,23 @@ def main(args):
                            blurring_images=True, gpu_blur=args.gpu_blur, expand_target_boxes=args.expand_target_boxes,
                            use_custom_image_norm=args.use_custom_image_norm, add_noise=args.add_noise, noise_level=args.noise_level,
                            add_block=args.add_block, add_jpeg_artifact=args.add_jpeg_artefacts, blur_acc_mode=args.blur_acc_mode,
-                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **deblur_kw, **deconvolve_kw, **ens_kw)
+                           image_output_folder=pictures("P%g_E%g" % (param, fraction)), **deblur_kw, **deconvolve_kw, **ens_kw, **metrics_kw)
             results["P%dE%d" % (param_index, fraction_index - 1)] = out
             if utils.is_main_process():
                 log_coco_stats(writer, "P" + str(param_index), out, fraction_index)
             print("P%d E%d: %d images, routes %s" % (param_index, fraction_index - 1, len(out["detections"]), out["routes"][:8]))
+            if "restoration" in out:
+                from .quality import format_restoration
+                res = out["restoration"]
+                print("P%d E%d: %s" % (param_index, fraction_index - 1, format_restoration(res)))
+                if writer is not None:
+                    for name, r in res.items():
+                        if isinstance(r, dict):
+                            writer.add_scalar("restoration/P%d/%s_psnr_db" % (param_index, name), r["psnr_db"], fraction_index)
+                            writer.add_scalar("restoration/P%d/%s_ssim" % (param_index, name), r["ssim"], fraction_index)
+                    for gain in ("psnr_gain_db", "ssim_gain"):
+                        if gain in res:
+                            writer.add_scalar("restoration/P%d/%s" % (param_index, gain), res[gain], fraction_index)
     if writer is not None:
         writer.close()
     return results

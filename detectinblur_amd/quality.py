@@ -19,6 +19,11 @@ CUDA tensors take the HIP entry on the current stream (two launches, no synchron
 CPU tensors take `psnr_ssim_torch`, the plain-torch restatement of the definition with the same window, in float64 (in float32 on
 request: that form, shifted by L / 2, is what the HIP path's time is measured against on the GPU).
 
+`restoration_quality(ref, candidates)` scores one or two candidates against one sharp image in one pass (include/dib.h,
+dib_restoration_quality; csrc/dib_restoration.hip): the sharp image is read once, every candidate's figures are `psnr_ssim(candidate,
+ref)` bit for bit, optionally on 8-bit grey levels, and an accumulator on the device takes the per-image figures in.
+`RestorationMeter` is that accumulator for one sweep cell (`evaluate.py --restoration_metrics`): no read before `result()`.
+
 No accuracy claim: PSNR and SSIM of synthetic images say how well a stage restores those images, nothing about detection AP."""
 import math
 
@@ -124,6 +129,197 @@ def psnr_ssim_hip(a, b, data_range=1.0, out=None, work=None):
     _lib.check(_lib.lib().dib_image_quality(a.data_ptr(), blur_ops._DT[a.dtype], b.data_ptr(), blur_ops._DT[b.dtype], C, H, W, L,
                                             out.data_ptr(), work.data_ptr(), _lib.stream_of(a)))
     return out
+
+
+ACC_DOUBLES = 6          # include/dib.h DIB_RQ_ACC_DOUBLES: n, n_identical, n_nonfinite, sum_mse, sum_psnr_db, sum_ssim
+MAX_CANDIDATES = 2
+
+
+def grey8(x):
+    """the 8-bit grey levels of a [0, 1] image as fp32: round(clamp(255 x, 0, 255)), ties to even, a NaN stays a NaN -- what
+    dib_restoration_quality does to every pixel it reads under quantize8"""
+    return torch.round(torch.clamp(x.float() * 255, 0, 255))
+
+
+def _check_restoration(ref, candidates, quantize, data_range):
+    if isinstance(candidates, torch.Tensor):
+        candidates = [candidates]
+    candidates = list(candidates)
+    if not 1 <= len(candidates) <= MAX_CANDIDATES:
+        raise ValueError("restoration_quality: %d candidates, 1 or 2 are supported" % len(candidates))
+    for c in candidates:
+        L = _check(c, ref, data_range)
+    if quantize and L != 1.0:
+        raise ValueError("restoration_quality: quantize8 takes images in [0, 1]: data_range must be 1, got %r" % (data_range,))
+    return candidates, L
+
+
+def _check_buffers(out, acc, K, ref):
+    if out is not None and (out.dtype != torch.float32 or out.numel() != 3 * K or not out.is_contiguous() or out.device != ref.device):
+        raise ValueError("restoration_quality: out must be %d contiguous float32 elements on the images' device" % (3 * K))
+    if acc is not None and (acc.dtype != torch.float64 or acc.numel() < ACC_DOUBLES * K or not acc.is_contiguous() or acc.device != ref.device):
+        raise ValueError("restoration_quality: acc must be at least %d contiguous float64 elements on the images' device" % (ACC_DOUBLES * K))
+
+
+def fold(acc_row, figures):
+    """dib_restoration_quality's accumulator rule on the host: `figures` = (mse, psnr_db, ssim) as fp32 values, `acc_row` a list of
+    ACC_DOUBLES floats, updated in place"""
+    mse, psnr, ssim = (float(v) for v in figures)
+    if not (math.isfinite(mse) and math.isfinite(ssim)):
+        acc_row[2] += 1.0
+        return acc_row
+    acc_row[0] += 1.0
+    acc_row[3] += mse
+    acc_row[5] += ssim
+    if mse == 0.0:
+        acc_row[1] += 1.0
+    else:
+        acc_row[4] += psnr
+    return acc_row
+
+
+@torch.no_grad()
+def restoration_quality_torch(ref, candidates, quantize8=False, data_range=1.0, out=None, acc=None):
+    """the plain-torch form of restoration_quality: psnr_ssim_torch(candidate, ref) in float64 per candidate, on 8-bit grey levels with
+    L = 255 under `quantize8`; the accumulator is folded on the host (this path reads its results)"""
+    candidates, L = _check_restoration(ref, candidates, quantize8, data_range)
+    K = len(candidates)
+    _check_buffers(out, acc, K, ref)
+    rows = [psnr_ssim_torch(grey8(c), grey8(ref), 255.0) if quantize8 else psnr_ssim_torch(c, ref, L) for c in candidates]
+    res = torch.cat(rows)
+    if acc is not None:
+        host = acc.detach().cpu().tolist()
+        for k, row in enumerate(rows):
+            host[ACC_DOUBLES * k:ACC_DOUBLES * (k + 1)] = fold(host[ACC_DOUBLES * k:ACC_DOUBLES * (k + 1)], row.tolist())
+        acc.copy_(torch.tensor(host, dtype=torch.float64))
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def restoration_workspace_bytes(K, C, H, W):
+    from . import _lib
+    return int(_lib.lib().dib_restoration_quality_workspace_bytes(int(K), int(C), int(H), int(W)))
+
+
+@torch.no_grad()
+def restoration_quality_hip(ref, candidates, quantize8=False, data_range=1.0, out=None, acc=None, work=None):
+    """dib_restoration_quality on CUDA images, on the current stream: two launches whatever the number of candidates, nothing waits."""
+    from . import _lib, blur_ops
+    candidates, L = _check_restoration(ref, candidates, quantize8, data_range)
+    if not ref.is_cuda:
+        raise TypeError("restoration_quality_hip needs CUDA images")
+    K = len(candidates)
+    _check_buffers(out, acc, K, ref)
+    C, H, W = (int(v) for v in ref.shape)
+    if out is None:
+        out = torch.empty(3 * K, dtype=torch.float32, device=ref.device)
+    need = restoration_workspace_bytes(K, C, H, W)
+    if work is None:
+        work = torch.empty(need // 8, dtype=torch.float64, device=ref.device)
+    elif work.numel() * work.element_size() < need or not work.is_contiguous() or work.device != ref.device:
+        raise ValueError("restoration_quality_hip: work must hold %d contiguous bytes on the images' device" % need)
+    _lib.check(_lib.lib().dib_restoration_quality(ref.data_ptr(), blur_ops._DT[ref.dtype], _lib.ptr_array([c.data_ptr() for c in candidates]),
+                                                  _lib.int_array([blur_ops._DT[c.dtype] for c in candidates]), K, C, H, W, int(bool(quantize8)), L,
+                                                  out.data_ptr(), None if acc is None else acc.data_ptr(), work.data_ptr(), _lib.stream_of(ref)))
+    return out
+
+
+def restoration_quality(ref, candidates, quantize8=False, data_range=1.0, out=None, acc=None, work=None):
+    """ref: the sharp image; candidates: one or two images (a tensor or a sequence) to score against it; all planar C x H x W, contiguous,
+    Half or fp32 in any mix, on one device.  Returns (or fills `out` with) 3 K fp32 elements: mse, psnr_db, ssim per candidate -- with
+    quantize8 off exactly psnr_ssim(candidate, ref), bit for bit on the HIP path.  `quantize8`: every image is scored as its 8-bit grey
+    levels (`grey8`), L = 255; data_range must be 1.  `acc`: ACC_DOUBLES float64 elements per candidate on the images' device,
+    updated in place: n, n_identical (mse == 0: +inf dB, left out of the PSNR sum), n_nonfinite (NaN or infinite mse or ssim: counted,
+    nothing added), sum_mse, sum_psnr_db, sum_ssim of the fp32 figures.  CUDA images take the HIP entry on the current stream (an error
+    when the library is missing); CPU images the torch restatement."""
+    if isinstance(ref, torch.Tensor) and ref.is_cuda:
+        return restoration_quality_hip(ref, candidates, quantize8, data_range, out, acc, work)
+    return restoration_quality_torch(ref, candidates, quantize8, data_range, out, acc)
+
+
+class RestorationMeter(object):
+    """One sweep cell's restoration figures (engine.evaluate(restoration_metrics=True)): per image the blurred one and, when a stage ran,
+    the restored one against the sharp image, accumulated on the images' device.  Owns the accumulator, the workspace and the 3 K
+    results; `update` queues two launches on the current stream and reads nothing; `result` makes the one device read of the cell."""
+
+    def __init__(self, device, quantize8=False, names=("blurred", "restored")):
+        if not 1 <= len(names) <= MAX_CANDIDATES:
+            raise ValueError("RestorationMeter: %d names, 1 or 2 are supported" % len(names))
+        self.device, self.quantize8, self.names = torch.device(device), bool(quantize8), tuple(names)
+        self.acc = torch.zeros(ACC_DOUBLES * len(self.names), dtype=torch.float64, device=self.device)
+        self.out = torch.zeros(3 * len(self.names), dtype=torch.float32, device=self.device)
+        self.work, self.skipped = None, 0
+
+    def reset(self):
+        self.acc.zero_()
+        self.skipped = 0
+
+    def skip(self, n=1):
+        """an image that was not blurred: nothing to compare"""
+        self.skipped += int(n)
+
+    def _workspace(self, shape):
+        """sized for the largest image seen, for every name; regrown outside any capture (the old one goes back to torch's allocator,
+        which keeps it until the launches queued on this stream are through)"""
+        need = restoration_workspace_bytes(len(self.names), *shape)
+        if self.work is None or self.work.numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("RestorationMeter: the workspace has to grow for image %s; run one update of the largest image "
+                                   "before capturing" % (tuple(shape),))
+            self.work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        return self.work
+
+    def update(self, sharp, blurred, restored=None):
+        candidates = [blurred] if restored is None else [blurred, restored]
+        if len(candidates) > len(self.names):
+            raise ValueError("RestorationMeter: a restored image for a meter with names %s" % (self.names,))
+        for c in candidates:
+            if c.shape != sharp.shape:
+                raise ValueError("RestorationMeter: image %s against a sharp image %s" % (tuple(c.shape), tuple(sharp.shape)))
+        K = len(candidates)
+        work = self._workspace(sharp.shape) if sharp.is_cuda else None
+        return restoration_quality(sharp, candidates, self.quantize8, 1.0, self.out[:3 * K], self.acc[:ACC_DOUBLES * K], work)
+
+    def result(self):
+        """one device read, then -- with a process group up -- one all_reduce of the 6 K doubles and the skip count: a collective on
+        every rank, whether its shard was empty or not"""
+        import torch.distributed as dist
+        t = torch.cat([self.acc.detach().cpu(), torch.tensor([float(self.skipped)], dtype=torch.float64)])
+        if dist.is_available() and dist.is_initialized():
+            t = t.to(self.device) if dist.get_backend() == "nccl" else t
+            dist.all_reduce(t)
+            t = t.cpu()
+        v = t.tolist()
+        L = 255.0 if self.quantize8 else 1.0
+        nan = float("nan")
+        res = {"skipped": int(v[-1]), "quantize8": self.quantize8}
+        for k, name in enumerate(self.names):
+            n, same, bad, s_mse, s_psnr, s_ssim = v[ACC_DOUBLES * k:ACC_DOUBLES * (k + 1)]
+            mse = s_mse / n if n else nan
+            res[name] = {"images": int(n), "identical": int(same), "nonfinite": int(bad), "mse": mse,
+                         "psnr_db": s_psnr / (n - same) if n > same else nan,
+                         "psnr_of_mean_mse_db": (float("inf") if mse == 0 else 10.0 * math.log10(L * L / mse)) if n else nan,
+                         "ssim": s_ssim / n if n else nan}
+        if len(self.names) == 2 and res[self.names[1]]["images"] > 0:
+            a, b = res[self.names[0]], res[self.names[1]]
+            res["psnr_gain_db"] = b["psnr_db"] - a["psnr_db"]
+            res["ssim_gain"] = b["ssim"] - a["ssim"]
+        return res
+
+
+def format_restoration(res):
+    """one line for a cell's `RestorationMeter.result()`"""
+    parts = []
+    for name, r in res.items():
+        if isinstance(r, dict):
+            parts.append("%s PSNR %.2f dB, SSIM %.4f (%d images%s%s)" % (name, r["psnr_db"], r["ssim"], r["images"],
+                                                                       ", %d identical" % r["identical"] if r["identical"] else "",
+                                                                       ", %d not finite" % r["nonfinite"] if r["nonfinite"] else ""))
+    if "psnr_gain_db" in res:
+        parts.append("gain %+.2f dB, %+.4f SSIM" % (res["psnr_gain_db"], res["ssim_gain"]))
+    return "Restoration%s: %s; %d not blurred (no quality claim)" % (" (8-bit)" if res.get("quantize8") else "", "; ".join(parts), res["skipped"])
 
 
 def psnr_ssim(a, b, data_range=1.0, out=None):

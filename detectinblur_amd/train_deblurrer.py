@@ -327,8 +327,8 @@ def validate(dataset, args, device, K):
             inp += psnr(blurred[0], sharp[0])
             n += 1
             if min(sharp[0].shape[-2:]) >= quality.TAPS:      # (a side below the 11-pixel window has no SSIM)
-                ssims.append(torch.stack([quality.psnr_ssim(_planar(deblurred), _planar(sharp[0]))[2],
-                                          quality.psnr_ssim(_planar(blurred[0]), _planar(sharp[0]))[2]]))
+                # one pass for both: the sharp image is read once (bit for bit the two psnr_ssim calls it replaces)
+                ssims.append(quality.restoration_quality(_planar(sharp[0]), [_planar(deblurred), _planar(blurred[0])])[2::3])
         ssim_out, ssim_inp = torch.stack(ssims).double().mean(0).tolist() if ssims else (float("nan"), float("nan"))
         return (out / n, inp / n, ssim_out, ssim_inp, len(ssims)) if n else (float("nan"),) * 4 + (0,)
     finally:

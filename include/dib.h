@@ -745,6 +745,37 @@ int dib_image_quality(const void *a_dev, int a_dtype, const void *b_dev, int b_d
                       float *out_dev /* [3]: mse, psnr_db, ssim */, void *work_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Restoration quality of K = 1 or 2 candidates against ONE sharp image, in one pass, folded into a per-cell accumulator on the device
+ * (this library's addition; quality.py: restoration_quality, RestorationMeter; `evaluate.py --restoration_metrics`: the blurred image
+ * and what --deblur_first / --deconvolve_first make of it, against the image before the blur).
+ * ref_dev and cand_dev[k] (cand_dev, cand_dtype: HOST arrays of K entries): planar C x H x W, contiguous, each DIB_F16 or DIB_F32 in
+ * any mix, aligned to their element type only.  The definition is dib_image_quality's (window, valid windows, population moments,
+ * C1, C2), and with quantize8 == 0
+ *     out_dev[3 k .. 3 k + 2] == what dib_image_quality(cand_dev[k], ref_dev, ..., data_range) writes, BIT FOR BIT:
+ * both entries run the same device code per pair; this one reads the sharp image once and launches twice whatever K is.
+ * quantize8 != 0: every image is replaced as it is read by its 8-bit grey levels rintf(clamp(255 x, 0, 255)) in fp32 (ties to even,
+ * a NaN stays a NaN) and the metric runs on those with L = 255; data_range must then be 1.  Bit for bit dib_image_quality of images
+ * quantised that way beforehand, with data_range 255.  (A pixel k / 255 held in Half comes back as exactly k.)
+ * acc_dev (may be NULL): DIB_RQ_ACC_DOUBLES doubles per candidate, updated in place by one lane of the second launch:
+ *     {n, n_identical, n_nonfinite, sum_mse, sum_psnr_db, sum_ssim}
+ * from the figures AS WRITTEN to out_dev (fp32, widened): mse or ssim not finite -> n_nonfinite += 1 and nothing else;  mse == 0 ->
+ * n, n_identical += 1, sum_ssim += ssim (its +inf dB stays out of sum_psnr_db: the mean PSNR is over n - n_identical images);
+ * otherwise n += 1 and the three sums grow.  That is exactly what a host loop over the per-image out_dev rows would add, in order.
+ * Calls on one stream are ordered; there are no atomics, no allocation, no host synchronisation: capturable, the same bytes from run
+ * to run.  work_dev: dib_restoration_quality_workspace_bytes(K, C, H, W) bytes (0 for arguments the entry refuses), 8-byte aligned;
+ * nothing beyond is written.
+ * DIB_EINVAL (nothing launched): K outside 1..2, null pointer (acc_dev excepted), unknown dtype, C, H or W < 1, data_range <= 0 or not
+ * finite, quantize8 with data_range != 1, a misaligned pointer (out_dev: 4 bytes, acc_dev and work_dev: 8), out_dev, acc_dev or
+ * work_dev overlapping an input or each other (the inputs may overlap or be one another: they are only read).
+ * DIB_ESHAPE: H < 11 or W < 11, or C H W >= 2^31 - 1.
+ * ------------------------------------------------------------------------------------- */
+#define DIB_RQ_ACC_DOUBLES 6
+size_t dib_restoration_quality_workspace_bytes(int K, int C, int H, int W);
+int dib_restoration_quality(const void *ref_dev, int ref_dtype, const void *const *cand_dev, const int *cand_dtype, int K, int C, int H,
+                            int W, int quantize8, float data_range, float *out_dev /* [3 K]: mse, psnr_db, ssim per candidate */,
+                            double *acc_dev, void *work_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training DeepDeblur's network (`python -m detectinblur_amd.train_deblurrer`, models/deblur_train.py; the reference vendors the
  * trainer as models/deblur/train.py, dataCommon.py): what runs around MIOpen's convolutions and is not above already.  HBM-bound
  * streams on `stream`; no allocation, no atomics, no host synchronisation: capturable, and bitwise reproducible from call to call.
