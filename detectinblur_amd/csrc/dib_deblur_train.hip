@@ -28,7 +28,9 @@
 //       slice's workgroup adds |d| of elements slice_begin + t, + 256, ...: a chain of L = ceil(slice length / 256); the 256 lanes
 //       are added as a tree of 8 levels; the second launch adds the S partial sums in slice order, divides by float(3 n_pix) and adds
 //       the result to the loss scalar.  DEPTH = L + 8 + S - 1 additions, then one division and one addition onto the scalar.
-// models/deblur_train.py restates both geometries (bias_grad_depth, l1_loss_depth) for the tests' error bounds.
+// models/deblur_train.py restates both geometries (bias_grad_depth, l1_loss_depth) for the tests' error bounds.  The order itself is
+// restated in numpy float32 from this comment (tests/test_deblur_train.py: restated_bias_grad, restated_l1), and
+// tests/test_deblur_train_geometry_gpu.py holds the kernels to it bit for bit at S = 1024: change the order here and there together.
 #include "dib_eltwise_vec.h"      // host side: misaligned, launch; F32Lane::select, F16Lane::select
 
 namespace dib {

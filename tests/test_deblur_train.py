@@ -1,6 +1,9 @@
 """The DeepDeblur trainer without a GPU: the draw order and the patch geometry against the reference's dataCommon.py (which imports
 scikit-image and cannot be imported here: its order is restated below with line citations), the torch restatements of the two
-reduction kernels against float64 definitions, the torch path of the network, and the driver end to end on the CPU."""
+reduction kernels against float64 definitions, their summation order restated in numpy float32 from the header of
+csrc/dib_deblur_train.hip (against float64 sums and against the two depth helpers; tests/test_deblur_train_geometry_gpu.py holds the
+kernels to it bit for bit), the torch path of the network, and the driver end to end on the CPU."""
+import collections
 import contextlib
 import io
 import os
@@ -133,6 +136,205 @@ def test_depth_formulas_of_the_summation_trees():
     assert DT.bias_grad_depth(16 * 256 * 256, 64) == 64 + 4 + 1023  # the trainer's default level 0
     assert DT.l1_loss_depth(1) == 1 + 8 + 0
     assert DT.l1_loss_depth(1027) == 7 + 8 + 1                      # 3081 elements: 2 slices of <= 1541: L = 7
+
+
+# ---- THE SUMMATION ORDER, restated in numpy float32 -----------------------------------------------------------------------------
+# Written from the header comment of csrc/dib_deblur_train.hip ("THE SUMMATION ORDER ... fixed by the shape alone"), not from the
+# kernel bodies: tests/test_deblur_train_geometry_gpu.py holds the kernels to these bit for bit.  Both reductions have one structure:
+# n items in memory order are cut into S slices of consecutive items; W lanes walk a slice, lane w adding items w, w + W, ... one
+# after the other; the W lane sums are added as a tree; the S slice sums are added one after the other from slice 0.  `_walk` states
+# that structure once, over an algebra: `_F32` carries the values (every addition rounds once), `_Depth` carries, instead of a value,
+# the largest number of additions any one input has passed through on its way into it -- what DT.bias_grad_depth / DT.l1_loss_depth
+# claim to be -- and needs no data, only the geometry.
+
+BiasGradShape = collections.namedtuple("BiasGradShape", "V QB R chunks S L")
+
+
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
+def slice_begins(n, S):
+    """begin of slice s = 0..S (S: the end): the first n % S slices are one item longer"""
+    s = np.arange(S + 1, dtype=np.int64)
+    return n // S * s + np.minimum(n % S, s)
+
+
+def bias_grad_shape(n_pix, C, V):
+    """(b) of the header: V channels per lane, QB = min(C / V, 256) lane columns and R = 256 / QB pixel rows per workgroup, `chunks`
+    workgroups side by side, S = ceil(n_pix / (16 R)) slices capped at 1024, L = ceil(longest slice / R) additions per lane."""
+    QB = min(C // V, 256)
+    R = 256 // QB
+    S = max(1, min(1024, _ceil_div(n_pix, 16 * R)))
+    L = _ceil_div(int(np.diff(slice_begins(n_pix, S)).max()), R)
+    return BiasGradShape(V, QB, R, _ceil_div(C // V, QB), S, L)
+
+
+def l1_shape(n_pix):
+    """(c) of the header: (S, L) of the 3 n_pix differences: S = ceil(3 n_pix / 2048) capped at 1024, L = ceil(longest slice / 256)"""
+    S = max(1, min(1024, _ceil_div(3 * n_pix, 2048)))
+    return S, _ceil_div(int(np.diff(slice_begins(3 * n_pix, S)).max()), 256)
+
+
+class _F32:
+    def __init__(self, items):
+        self.items = np.ascontiguousarray(items, dtype=np.float32)             # [n, ...]
+
+    def zero(self, S, W):
+        return np.zeros((S, W) + self.items.shape[1:], dtype=np.float32)
+
+    def chain(self, acc, idx, valid):
+        x = self.items[np.minimum(idx, len(self.items) - 1)]
+        x[~valid] = 0                               # a lane past its slice's end adds nothing; x + 0 == x bit for bit (no sum here is -0)
+        return acc + x
+
+    @staticmethod
+    def add(a, b):
+        return a + b
+
+
+class _Depth:
+    EMPTY = -(1 << 40)                              # a sum that no input has entered yet
+
+    def zero(self, S, W):
+        return np.full((S, W), self.EMPTY, dtype=np.int64)
+
+    def chain(self, acc, idx, valid):
+        return np.where(valid, np.maximum(acc, 0) + 1, acc)      # the item comes with no addition behind it
+
+    @staticmethod
+    def add(a, b):
+        return np.maximum(a, b) + 1
+
+
+def _walk(n, S, W, ops):
+    begin = slice_begins(n, S)
+    lanes = np.arange(W, dtype=np.int64)
+    acc = ops.zero(S, W)
+    for j in range(_ceil_div(int(np.diff(begin).max()), W)):     # the lane chain, in item order: w, w + W, w + 2 W, ...
+        idx = begin[:-1, None] + lanes[None, :] + j * W
+        acc = ops.chain(acc, idx, idx < begin[1:, None])
+    h = 1
+    while h < W:
+        h *= 2
+    h //= 2
+    while h >= 1:                                   # the tree: row r takes row r + h, largest h first, only where r + h < W
+        m = min(h, W - h)
+        acc[:, :m] = ops.add(acc[:, :m], acc[:, h:h + m])
+        h //= 2
+    total = acc[0, 0]
+    for s in range(1, S):                           # the slices, one after the other from slice 0
+        total = ops.add(total, acc[s, 0])
+    return total
+
+
+def restated_bias_grad(values, V):
+    """fp32 `values` [n_pix, C] (the masked gradient; Half values are exact in fp32) -> bias_grad [C] in the header's order"""
+    n_pix, C = values.shape
+    g = bias_grad_shape(n_pix, C, V)
+    return _walk(n_pix, g.S, g.R, _F32(values))
+
+
+def restated_bias_grad_depth(n_pix, C, V):
+    g = bias_grad_shape(n_pix, C, V)
+    return int(_walk(n_pix, g.S, g.R, _Depth()))
+
+
+def restated_l1(out, target, stride, gscale, loss=0.0):
+    """fp32 out [n_pix, 3], target [n_pix, stride] -> (the loss scalar after this level, the gradient [n_pix, 3]) in the header's
+    order: out - target in fp32, fabsf, the chain with stride 256, eight tree levels, the slices from slice 0, one division by
+    float(3 n_pix), one addition onto the scalar."""
+    out = np.asarray(out, dtype=np.float32).reshape(-1, 3)
+    n = out.size
+    d = out - np.asarray(target, dtype=np.float32).reshape(-1, stride)[:, :3]
+    total = _walk(n, l1_shape(n // 3)[0], 256, _F32(np.abs(d).reshape(-1)))
+    denom = np.float32(n)
+    k = np.float32(gscale) / denom
+    grad = np.where(d != d, d, np.where(d > 0, k, np.where(d < 0, -k, np.float32(0)))).astype(np.float32)
+    return np.float32(loss) + total / denom, grad
+
+
+def restated_l1_depth(n_pix):
+    return int(_walk(3 * n_pix, l1_shape(n_pix)[0], 256, _Depth()))
+
+
+def _real_draw(rs, *shape):
+    """the GPU tests' draw, randn * exp(6 rand): magnitudes spread over e^6, so that the order of the additions shows in the result"""
+    return (rs.standard_normal(shape) * np.exp(6 * rs.random_sample(shape))).astype(np.float32)
+
+
+# (n_pix, C, V): every V; R from 1 to 128 and 85 (no power of two); one and several slices, even and uneven; one and two chunks
+SMALL_BIAS_GRAD = [(1, 64, 4), (5, 3, 1), (255, 12, 4), (257, 3, 1), (4099, 64, 4), (2049, 8, 4), (4099, 8, 4), (300, 8, 8),
+                   (1000, 64, 8), (700, 64, 1), (37, 1028, 4), (5, 2056, 8), (4099, 12, 1)]
+# ... and shapes at and past the 1024-slice cap, the trainer's own call last: for the depth alone, which needs no data
+CAPPED_BIAS_GRAD = [(1392640, 3, 1), (1392641, 3, 1), (262144, 64, 4), (262145, 64, 4), (600001, 64, 4), (16385, 1024, 4),
+                    (16391, 1028, 4), (524289, 64, 8), (16385, 2056, 8), (65537, 64, 1), (16 * 256 * 256, 64, 4)]
+SMALL_L1 = [1, 7, 29, 683, 1027, 4099]
+CAPPED_L1 = [170000, 699050, 699051, 1048576]
+
+
+@pytest.mark.parametrize("n_pix,C,V", SMALL_BIAS_GRAD)
+def test_restated_bias_grad_against_float64(n_pix, C, V):
+    values = _real_draw(np.random.RandomState(1000 * C + n_pix), n_pix, C)
+    got = restated_bias_grad(values, V)
+    assert got.dtype == np.float32 and got.shape == (C,)
+    v64 = values.astype(np.float64)
+    bound = DT.bias_grad_depth(n_pix, C, V) * 2.0 ** -24 * np.abs(v64).sum(0)
+    assert (np.abs(got.astype(np.float64) - v64.sum(0)) <= bound).all()
+
+
+@pytest.mark.parametrize("n_pix", SMALL_L1)
+def test_restated_l1_against_float64(n_pix):
+    rs = np.random.RandomState(n_pix)
+    out, target = _real_draw(rs, n_pix, 3), _real_draw(rs, n_pix, 6)
+    target[0, 1] = out[0, 1]
+    loss, grad = restated_l1(out, target, 6, 0.5, loss=3.0)
+    assert loss.dtype == np.float32 and grad.dtype == np.float32
+    d = out.astype(np.float64) - target[:, :3].astype(np.float64)
+    want = np.abs(d).sum() / (3 * n_pix)
+    # the subtraction, the tree, the division, the addition onto the scalar
+    assert abs(float(loss) - (3.0 + want)) <= (DT.l1_loss_depth(n_pix) + 3) * 2.0 ** -24 * (3.0 + want)
+    k = np.float32(0.5) / np.float32(3 * n_pix)
+    assert np.array_equal(grad.astype(np.float64), np.sign(d) * float(k)) and grad[0, 1] == 0
+
+
+@pytest.mark.parametrize("n_pix,C,V", SMALL_BIAS_GRAD + CAPPED_BIAS_GRAD)
+def test_bias_grad_depth_is_the_restated_orders_longest_chain(n_pix, C, V):
+    g = bias_grad_shape(n_pix, C, V)
+    assert restated_bias_grad_depth(n_pix, C, V) == DT.bias_grad_depth(n_pix, C, V) == g.L + (g.R - 1).bit_length() + g.S - 1
+    if (n_pix, C, V) in CAPPED_BIAS_GRAD:
+        assert g.S == 1024 and n_pix >= 16 * g.R * 1024
+
+
+@pytest.mark.parametrize("n_pix", SMALL_L1 + CAPPED_L1)
+def test_l1_loss_depth_is_the_restated_orders_longest_chain(n_pix):
+    S, L = l1_shape(n_pix)
+    assert restated_l1_depth(n_pix) == DT.l1_loss_depth(n_pix) == L + 8 + S - 1
+    assert (S == 1024) == (n_pix >= 699050)
+
+
+def test_restated_order_is_not_any_order():
+    """the restatement can tell the header's tree (largest h first) from the same additions smallest h first, on the GPU tests' draw"""
+    values = _real_draw(np.random.RandomState(3), 4099, 8)
+    g = bias_grad_shape(4099, 8, 4)
+    assert (g.R, g.S) == (128, 3)
+    lanes = _F32(values)
+    acc = lanes.zero(g.S, g.R)
+    begin = slice_begins(4099, g.S)
+    for j in range(g.L):
+        idx = begin[:-1, None] + np.arange(g.R)[None, :] + j * g.R
+        acc = lanes.chain(acc, idx, idx < begin[1:, None])
+    h = 1
+    while h < g.R:                                  # smallest h first: still a sum of every lane, another order
+        half = acc[:, ::2 * h].copy()
+        half += acc[:, h::2 * h]
+        acc[:, ::2 * h] = half
+        h *= 2
+    other = acc[0, 0] + acc[1, 0] + acc[2, 0]
+    want = restated_bias_grad(values, 4)
+    v64 = values.astype(np.float64)
+    assert (np.abs(other.astype(np.float64) - v64.sum(0)) <= DT.bias_grad_depth(4099, 8) * 2.0 ** -24 * np.abs(v64).sum(0)).all()
+    assert other.tobytes() != want.tobytes()
 
 
 # ---- the network's torch path ---------------------------------------------------------------------------------------------------
