@@ -190,6 +190,10 @@ _SIGNATURES = {
     # the DeepDeblur trainer (models/deblur_train.py): patch gather, epilogue backward with the bias gradient, L1 loss of a level
     "dib_deblur_patches": (ctypes.c_int, [_c_void_pp, ctypes.c_int, _c_int_p, _c_int_p, _c_int_p, _c_int_p, ctypes.POINTER(ctypes.c_uint),
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # ... with dataCommon's saturation change and add_noise in the same launch (--change_saturation, --patch_noise_sigma)
+    "dib_deblur_patches_augment": (ctypes.c_int, [_c_void_pp, ctypes.c_int, _c_int_p, _c_int_p, _c_int_p, _c_int_p, ctypes.POINTER(ctypes.c_uint),
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint),
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "dib_bias_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
     "dib_bias_grad_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -5,10 +5,18 @@ model.py); `python -m detectinblur_amd.train_deblurrer` is this project's, fed b
   draws     `draw_patch`: one patch origin and one augmentation per image from Python's `random`, in the order of the reference's
             dataCommon.py -- crop (:32-33) draws randrange for py, then for px; augment (:61-68) draws choice for hflip, for vflip and
             for rot90, then shuffles the channel order.  The patch is cropped first, then hflip (reverse x), vflip (reverse y),
-            rot90 (a transpose), then the channel order (:76-81).  The HSV saturation change (:72-87) and dataCommon's add_noise are
-            NOT built (the first needs scikit-image's colour conversions; noise is the blur stage's own --add_noise).
+            rot90 (a transpose), then the channel order (:76-81).  On request, then from `np.random` as the reference does: the
+            saturation factor uniform(0.5, 1.5) (:73), add_noise's sigma normal() * sigma_sigma (:48), and two 32-bit key words that
+            stand in for its randn field (:51).  With neither asked for, no generator sees an extra draw.
   patches   `gather_patches`: the patches of a ragged list of images as one planar [B, 3, ps, ps] tensor: dib_deblur_patches on the
             GPU (one launch, bit-exact data movement), `gather_patches_torch` elsewhere and as the reference of the tests.
+  values    `augment_patches`: the same patches with dataCommon's HSV saturation change (:83-87) and add_noise (:50-52) applied, as
+            fp32 grey levels / 255: dib_deblur_patches_augment on the GPU (one launch per list), `augment_patches_torch` elsewhere.
+            Scaling S in HSV and converting back has a closed form without the hue, x_c = clip(m - a (m - q_c), 0, 255) with m the
+            pixel's maximum (csrc/dib_deblur_augment.hip states the four steps), so no colour conversion is needed.  Two stated
+            readings: the patch is quantised to 8 bits first (the reference's `augment` runs on the uint8 array of an image file),
+            and the result is rounded to the nearest grey level, where the reference hands unrounded floats to its pyramid: at most
+            half a level, against a sigma of typically 2.
   pyramid   `patch_levels`: quantise to 8 bits, Gaussian pyramid, minus 127.5, per patch -- the inference stage's steps 1-3
             (dib_deblur_pyramid / deblur.quantise + deblur.pyramid), written into slab b of batched channels-last level tensors
             [B, 6, ps >> s, ps >> s] (coarsest: [B, 3, ...]); channels 3..5 are never written and never read.  n_scales launches per
@@ -48,6 +56,7 @@ import ctypes
 import math
 import random
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -64,13 +73,16 @@ FUSE_DEBLUR_TRAIN_AMP = True
 PATCH_HFLIP, PATCH_VFLIP, PATCH_ROT90 = 1, 2, 4          # include/dib.h DIB_PATCH_*
 PATCH_MAX_BATCH = 64                                     # images per dib_deblur_patches launch
 
-PatchDraw = collections.namedtuple("PatchDraw", "py px hflip vflip rot90 order")
+# saturation: augment's amp_factor; sigma: add_noise's, in grey levels (it may be negative: a normal draw); key: the noise field's
+PatchDraw = collections.namedtuple("PatchDraw", "py px hflip vflip rot90 order saturation sigma key", defaults=(1.0, 0.0, (0, 0)))
 
 
 # ---- draws -----------------------------------------------------------------------------------------------------------------------
 
-def draw_patch(h, w, ps):
-    """One image's draws, in dataCommon.py's order (crop :32-33, augment :61-68)."""
+def draw_patch(h, w, ps, change_saturation=False, noise_sigma=0.0):
+    """One image's draws, in dataCommon.py's order (crop :32-33, augment :61-68), from Python's `random`; then, only when asked for,
+    from `np.random` as the reference draws them: augment's amp_factor (:73), add_noise's sigma (:48, sigma_sigma = `noise_sigma`,
+    rgb_range = 255) and two 32-bit words, the key of the noise field that stands in for its randn (:51)."""
     py = random.randrange(0, h - ps + 1)
     px = random.randrange(0, w - ps + 1)
     choices = (False, True)
@@ -79,7 +91,14 @@ def draw_patch(h, w, ps):
     rot90 = random.choice(choices)
     order = list(range(3))
     random.shuffle(order)
-    return PatchDraw(py, px, hflip, vflip, rot90, tuple(order))
+    draw = PatchDraw(py, px, hflip, vflip, rot90, tuple(order))
+    if change_saturation:
+        draw = draw._replace(saturation=float(np.random.uniform(0.5, 1.5)))
+    if noise_sigma:
+        sigma = float(np.random.normal() * noise_sigma)
+        key = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint32)
+        draw = draw._replace(sigma=sigma, key=(int(key[0]), int(key[1])))
+    return draw
 
 
 def flags_word(draw):
@@ -128,6 +147,71 @@ def gather_patches(images, draws, ps):
     if images[0].is_cuda:
         return gather_patches_device(images, draws, ps)
     return gather_patches_torch(images, draws, ps)
+
+
+# ---- patches with the saturation change and the noise ----------------------------------------------------------------------------
+
+def noise_seed(key):
+    """The seed `augment_patches_torch` gives its torch.Generator for a draw's key.  torch's CPU generator reads the low 32 bits of a
+    seed only, so both words are mixed into those."""
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    return (k1 << 32) | (k0 ^ ((k1 * 0x9E3779B1) & 0xFFFFFFFF))
+
+
+def augment_patches_torch(images, draws, ps, noise, pre_rounding=False):
+    """planar [3, H_b, W_b] Half or fp32 images -> fp32 [B, 3, ps, ps]: `gather_patches_torch`, then csrc/dib_deblur_augment.hip's four
+    steps op for op in torch fp32 on the 0..255 scale -- quantise; x = clip(m - a (m - q), 0, 255) with m the pixel's maximum;
+    with `noise` and a sigma other than 0, x = clip(x + sigma n, 0, 255); round to the nearest level, / 255.  On a GPU it is bit-equal to
+    the kernel whenever sigma == 0.  THE NOISE FIELD n is torch.randn from a CPU torch.Generator seeded with the draw's key
+    (`noise_seed`): the kernel's field (Philox + Box-Muller on the element index) in distribution, NOT in bits.
+    pre_rounding (tests): the values before the last step, on the 0..255 scale."""
+    out = []
+    for img, d in zip(images, draws):
+        p = gather_patches_torch([img], [d], ps)[0]
+        q = deblur.quantise(p) + 0.0                      # (+ 0.0: a -0.0 that clamp may let through becomes the kernel's +0.0)
+        m = q.amax(0, keepdim=True)
+        t = (m - q) * float(np.float32(d.saturation))     # an exact integer times the fp32 factor: one rounding
+        x = (m - t).clamp(0, 255)
+        if noise and d.sigma != 0:
+            g = torch.Generator().manual_seed(noise_seed(d.key))
+            n = torch.randn((3, ps, ps), generator=g, dtype=torch.float32).to(x.device)
+            x = (x + n * float(np.float32(d.sigma))).clamp(0, 255)
+        # a true division: by a Python scalar, torch on a GPU multiplies by the rounded reciprocal instead
+        out.append(x if pre_rounding else x.round() / torch.full((), 255.0, dtype=torch.float32, device=x.device))
+    return torch.stack(out).contiguous()
+
+
+def augment_patches_device(images, draws, ps, noise):
+    from .. import _lib
+    first = images[0]
+    if first.dtype not in (torch.float16, torch.float32) or any(im.dtype != first.dtype or im.device != first.device or im.dim() != 3
+                                                                  or im.shape[0] != 3 for im in images):
+        raise ValueError("augment_patches: planar [3, H, W] Half or fp32 images of one dtype on one device")
+    images = [im.contiguous() for im in images]
+    out = torch.empty((len(images), 3, ps, ps), dtype=torch.float32, device=first.device)
+    dtype = _lib.DIB_F16 if first.dtype == torch.float16 else _lib.DIB_F32
+    for b0 in range(0, len(images), PATCH_MAX_BATCH):
+        # every per-image array is cut with the images
+        ims, ds = images[b0:b0 + PATCH_MAX_BATCH], draws[b0:b0 + PATCH_MAX_BATCH]
+        n = len(ims)
+        flags = (ctypes.c_uint * n)(*[flags_word(d) for d in ds])
+        saturation = (ctypes.c_float * n)(*[d.saturation for d in ds])
+        sigma = (ctypes.c_float * n)(*[d.sigma if noise else 0.0 for d in ds])
+        keys = (ctypes.c_uint * (2 * n))(*[int(k) & 0xFFFFFFFF for d in ds for k in d.key])
+        _lib.check(_lib.lib().dib_deblur_patches_augment(_lib.ptr_array([im.data_ptr() for im in ims]), dtype,
+                                                         _lib.int_array([int(im.shape[1]) for im in ims]),
+                                                         _lib.int_array([int(im.shape[2]) for im in ims]),
+                                                         _lib.int_array([d.py for d in ds]), _lib.int_array([d.px for d in ds]), flags,
+                                                         saturation, sigma, keys, n, ps, out[b0].data_ptr(), _lib.stream_of(first)))
+    return out
+
+
+def augment_patches(images, draws, ps, noise):
+    """The patches of `gather_patches` with each draw's saturation change and, with `noise` (the blurred input; the sharp target
+    passes False), its noise: fp32 [B, 3, ps, ps] holding grey levels / 255, ready for `patch_levels`."""
+    if images[0].is_cuda:
+        return augment_patches_device(images, draws, ps, noise)
+    return augment_patches_torch(images, draws, ps, noise)
 
 
 # ---- pyramid ---------------------------------------------------------------------------------------------------------------------

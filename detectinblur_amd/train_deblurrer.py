@@ -14,8 +14,13 @@ Adam.  The host reads the loss only every --print_freq steps: the step itself do
 Defaults are DeepDeblur's published ones (-b 16, --patch_size 256, --lr 1e-4, Adam (0.9, 0.999), --lr-steps 500 750 900, --lr-gamma
 0.5, --epochs 1000, 3 scales x 19 blocks x 64 features, 5 x 5 kernels, loss sum_s mean |out_s - target_s|, fp32).  Its option.py and
 loss/ are not in the reference tree: a STATED READING, not pinned.  Not built: the adversarial loss (discriminator.py), bf16
-training, dataCommon's saturation augmentation and add_noise, a batched pyramid kernel, tuned convolution choices.  No accuracy or
-PSNR claim is made anywhere: synthetic data shows nothing.
+training, a batched pyramid kernel, tuned convolution choices.  No accuracy or PSNR claim is made anywhere: synthetic data shows
+nothing.
+
+--change_saturation and --patch_noise_sigma S: the value half of dataCommon.py's recipe (augment's HSV saturation change :72-87; add_noise
+:43-54, DeepDeblur's S is 2), off by default.  Per image one factor uniform(0.5, 1.5) scales the saturation of both patches, and the
+blurred patch alone gets Gaussian noise of sigma normal() * S grey levels; both ride in the patch launch (models/deblur_train.py,
+"values"; csrc/dib_deblur_augment.hip).  With neither flag the step is call for call what it was.  --validate_images stays unaugmented.
 
 --amp (the reference's train.py:43-46, 97-103, deblurInterface.py:144-145): the mixed-precision step.  Half input pyramids and Half
 convolutions on fp32 master weights (models/deblur_train.py, "MIXED PRECISION"), the loss in fp32 on the upcast outputs, against fp32
@@ -85,6 +90,11 @@ def build_parser():
     p.add_argument("--validate_images", default=0, type=int, metavar="K")
     p.add_argument("--amp", action="store_true", help="mixed precision: Half convolutions on fp32 master weights, loss scaling")
     p.add_argument("--init_scale", default=DEFAULT_INIT_SCALE, type=float, help="--amp: the loss scale GradScaler starts from")
+    p.add_argument("--change_saturation", action="store_true",
+                   help="dataCommon.augment's change_saturation: S of both patches scaled by one uniform(0.5, 1.5) factor per image")
+    p.add_argument("--patch_noise_sigma", default=0.0, type=float, metavar="S",
+                   help="dataCommon.add_noise's sigma_sigma (DeepDeblur: 2), on the blurred patch only; 0: off.  Not --add_noise, which "
+                        "belongs to the blur stage")
     # the blur: the flags of train.py that the GPU blur reads
     p.add_argument("--gpu_blur", action="store_true", help="implied: the pairs are made by the GPU blur")
     p.add_argument("--cpu_blur", action="store_true", help="refused: the loader's FFT blur would leave no sharp original on the device")
@@ -127,6 +137,8 @@ def reject(args):
     args.gpu_blur = True
     reject_idle_blur_acc_mode(args)
     reject_idle_init_scale(args)
+    if not (math.isfinite(args.patch_noise_sigma) and args.patch_noise_sigma >= 0):
+        raise SystemExit("--patch_noise_sigma %g: needs a finite level of at least 0 (0: no noise)" % args.patch_noise_sigma)
     if "coco" not in args.dataset:
         raise SystemExit("--dataset %s: only COCO (and --synthetic) is built" % args.dataset)
 
@@ -223,10 +235,17 @@ class Trainer(object):
                 raise RuntimeError("no image of this rank's batch has both sides >= --patch_size %d: the ranks' steps would part" % ps)
             return None
         blurred, sharp = make_pairs([images_CPU[i] for i in keep], [blur_dicts[i] for i in keep], self.device, self.args, self.jpeg)
-        draws = [DT.draw_patch(int(im.shape[-2]), int(im.shape[-1]), ps) for im in sharp]
         amp = self.scaler is not None
-        inputs = DT.patch_levels(DT.gather_patches(blurred, draws, ps), self.args.n_scales, torch.float16 if amp else torch.float32)
-        targets = DT.patch_levels(DT.gather_patches(sharp, draws, ps), self.args.n_scales)
+        if self.args.change_saturation or self.args.patch_noise_sigma:
+            # dataCommon's augment on both patches with one factor, add_noise on the blurred one only (a stated reading: DESIGN.md 4)
+            draws = [DT.draw_patch(int(im.shape[-2]), int(im.shape[-1]), ps, self.args.change_saturation, self.args.patch_noise_sigma)
+                     for im in sharp]
+            inputs = DT.patch_levels(DT.augment_patches(blurred, draws, ps, True), self.args.n_scales, torch.float16 if amp else torch.float32)
+            targets = DT.patch_levels(DT.augment_patches(sharp, draws, ps, False), self.args.n_scales)
+        else:
+            draws = [DT.draw_patch(int(im.shape[-2]), int(im.shape[-1]), ps) for im in sharp]
+            inputs = DT.patch_levels(DT.gather_patches(blurred, draws, ps), self.args.n_scales, torch.float16 if amp else torch.float32)
+            targets = DT.patch_levels(DT.gather_patches(sharp, draws, ps), self.args.n_scales)
         outputs = list(self.net(*inputs))
         loss = DT.pyramid_l1_loss([o.float() for o in outputs] if amp else outputs, targets)
         self.optimizer.zero_grad(set_to_none=True)

@@ -794,6 +794,23 @@ int dib_restoration_quality(const void *ref_dev, int ref_dtype, const void *cons
 int dib_deblur_patches(const void *const *in_dev, int dtype, const int *H, const int *W, const int *py, const int *px,
                        const unsigned int *flags, int B, int ps, void *out_dev, void *stream);
 
+/* PATCHES WITH THE VALUE AUGMENTATION (dataCommon.py: augment's change_saturation :72-87, add_noise :43-54; csrc/dib_deblur_augment.hip).
+ * The arguments of dib_deblur_patches and the same data movement, plus per image a saturation factor, a noise sigma in grey levels and
+ * the two key words of its noise field (keys: HOST array [B][2]); out_dev: planar fp32 [B][3][ps][ps] whatever `dtype` is.  Per pixel, in
+ * fp32 on the 0..255 scale, every operation rounded on its own:
+ *     q_c = the image's 8-bit level (dib_deblur_pyramid's quantisation: trunc(v * 255) clamped to 0..255, NaN -> 0; a Half product is
+ *           rounded to Half first)
+ *     x_c = clamp(m - saturation * (m - q_c), 0, 255),  m = max(q_0, q_1, q_2)       scaling S in HSV and converting back, without the hue
+ *     x_c = clamp(x_c + sigma * n_i, 0, 255)  when sigma != 0                        n_i: the generator of dib_post_ops on element index
+ *                                                                                    i = (c * ps + y) * ps + x of the image's output patch
+ *     out = rint(x_c) / 255                                                          a grey level: dib_deblur_pyramid reads it back exactly
+ * saturation == 1 and sigma == 0 give q_c / 255.  One launch; B <= 64.
+ * DIB_EINVAL: as dib_deblur_patches; a saturation that is not finite or below 0; a sigma that is not finite; out_dev not 4-byte aligned.
+ * DIB_ESHAPE: a patch that leaves its image.  Nothing is launched on either. */
+int dib_deblur_patches_augment(const void *const *in_dev, int dtype, const int *H, const int *W, const int *py, const int *px,
+                               const unsigned int *flags, const float *saturation, const float *sigma, const unsigned int *keys /* [B][2] */,
+                               int B, int ps, float *out_dev, void *stream);
+
 /* BIAS GRADIENT: the backward pass of dib_bias_act_nhwc / dib_bias_act_mask_nhwc in one pass over a channels-last fp32 gradient
  * [n_pix][C]:
  *     grad_out[p][c] = mask bit ? grad_in[p][c] : 0        the mask of dib_bias_act_mask_nhwc; bit-identical to dib_relu_mask_backward;
