@@ -206,6 +206,16 @@ _SIGNATURES = {
     "dib_l1_pyramid_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "dib_l1_pyramid_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # the trainer's adversarial loss (models/deblur_adversarial.py): LeakyReLU with a sign mask, its backward, BCE against a constant label
+    "dib_leaky_relu_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_leaky_relu_mask_f16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    "dib_leaky_relu_mask_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong,
+                                                    ctypes.c_void_p]),
+    "dib_leaky_relu_mask_backward_f16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong,
+                                                        ctypes.c_void_p]),
+    "dib_adv_bce_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "dib_adv_bce_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
     # test hook, not part of the drop-in boundary
     "dib_sparse_blur_generic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,

@@ -13,9 +13,23 @@ Adam.  The host reads the loss only every --print_freq steps: the step itself do
 
 Defaults are DeepDeblur's published ones (-b 16, --patch_size 256, --lr 1e-4, Adam (0.9, 0.999), --lr-steps 500 750 900, --lr-gamma
 0.5, --epochs 1000, 3 scales x 19 blocks x 64 features, 5 x 5 kernels, loss sum_s mean |out_s - target_s|, fp32).  Its option.py and
-loss/ are not in the reference tree: a STATED READING, not pinned.  Not built: the adversarial loss (discriminator.py), bf16
-training, a batched pyramid kernel, tuned convolution choices.  No accuracy or PSNR claim is made anywhere: synthetic data shows
-nothing.
+loss/ are not in the reference tree: a STATED READING, not pinned.  Not built: bf16 training, a batched pyramid kernel, tuned
+convolution choices.  No accuracy or PSNR claim is made anywhere: synthetic data shows nothing.
+
+--loss (the reference's deblurInterface.py:184, default 1*L1): terms weight*NAME joined by +, names in either case; L1 and ADV are
+built, anything else is refused at start.  With the default the step is call for call what it was, no discriminator is constructed
+and the checkpoint stays {"G"}.  With ADV the reference's discriminator (models/deblur_adversarial.py; discriminator.py, built by
+model.py:31-34 whenever --loss contains adv) is trained beside the generator; --patch_size must be at least 193.  One step with ADV --
+like L1's, a STATED READING: DeepDeblur's loss/ package is not in the reference tree:
+    G forward as before; fake = finest output + 127.5, real = finest target + 127.5 (0..255, channels-last; Half under --amp);
+    D update:  opt_D.zero_grad; loss_d = BCE(D(fake.detach()), 0) + BCE(D(real), 1), one device scalar; backward; opt_D steps;
+    G update:  loss_g = BCE(D(fake), 1) through the unwrapped discriminator with its parameters' requires_grad off (no weight-gradient
+               convolutions, DistributedDataParallel's reducer not involved); total = w_L1 * L1 + w_ADV * loss_g; backward; opt_G steps.
+opt_D is Adam with G's lr, betas and fusedness and a MultiStepLR of its own on the same milestones.  Under --amp one GradScaler serves
+both: scale(loss_d).backward(); step(opt_D); scale(total).backward(); step(opt_G); update().  Nothing in the step reads the device.
+model-<N>.pt becomes {"G", "D"} (the reference's layout; `Deblurer` reads "G"), optim-<N>.pt gains optimizer_D and lr_scheduler_D, and
+--resume refuses a file written with another --loss.  Not built: other loss terms, more than one D update per step, fake and real
+through D as one batch, tuned records for D's convolutions, a Half loss kernel.
 
 --change_saturation and --patch_noise_sigma S: the value half of dataCommon.py's recipe (augment's HSV saturation change :72-87; add_noise
 :43-54, DeepDeblur's S is 2), off by default.  Per image one factor uniform(0.5, 1.5) scales the saturation of both patches, and the
@@ -90,6 +104,8 @@ def build_parser():
     p.add_argument("--validate_images", default=0, type=int, metavar="K")
     p.add_argument("--amp", action="store_true", help="mixed precision: Half convolutions on fp32 master weights, loss scaling")
     p.add_argument("--init_scale", default=DEFAULT_INIT_SCALE, type=float, help="--amp: the loss scale GradScaler starts from")
+    p.add_argument("--loss", default=DEFAULT_LOSS, help="terms weight*NAME joined by + (the reference's grammar); built: L1, ADV (the adversarial "
+                                                        "loss: trains the reference's discriminator beside the generator)")
     p.add_argument("--change_saturation", action="store_true",
                    help="dataCommon.augment's change_saturation: S of both patches scaled by one uniform(0.5, 1.5) factor per image")
     p.add_argument("--patch_noise_sigma", default=0.0, type=float, metavar="S",
@@ -116,6 +132,34 @@ def build_parser():
 
 
 DEFAULT_INIT_SCALE = 1024.0      # the reference's (deblurInterface.py:145)
+DEFAULT_LOSS = "1*L1"            # the reference's (deblurInterface.py:184)
+LOSS_NAMES = ("L1", "ADV")
+
+
+def parse_loss(spec):
+    """--loss -> {NAME: weight} in the order given.  The reference's grammar (terms weight*NAME joined by +), names in either case;
+    every refusal names the offending part."""
+    if not str(spec).strip():
+        raise SystemExit("--loss %r: needs at least one of %s, as weight*NAME" % (spec, " and ".join(LOSS_NAMES)))
+    out = {}
+    for term in str(spec).split("+"):
+        part = term.strip()
+        weight, star, name = part.partition("*")
+        if not star or not weight.strip():
+            raise SystemExit("--loss %s: the term %r has no weight; write weight*NAME, as in %s" % (spec, part, DEFAULT_LOSS))
+        try:
+            w = float(weight)
+        except ValueError:
+            raise SystemExit("--loss %s: the weight %r of the term %r is not a number" % (spec, weight.strip(), part))
+        if not (math.isfinite(w) and w > 0):
+            raise SystemExit("--loss %s: the weight %r of the term %r needs to be finite and above 0" % (spec, weight.strip(), part))
+        key = name.strip().upper()
+        if key not in LOSS_NAMES:
+            raise SystemExit("--loss %s: the loss %r is not built; %s are" % (spec, name.strip(), " and ".join(LOSS_NAMES)))
+        if key in out:
+            raise SystemExit("--loss %s: %s is given twice" % (spec, key))
+        out[key] = w
+    return out
 
 
 def reject_idle_init_scale(args):
@@ -137,6 +181,11 @@ def reject(args):
     args.gpu_blur = True
     reject_idle_blur_acc_mode(args)
     reject_idle_init_scale(args)
+    if "ADV" in parse_loss(args.loss):
+        from .models.deblur_adversarial import min_side
+        if args.patch_size < min_side(args.kernel_size):
+            raise SystemExit("--loss %s with --patch_size %d: the discriminator's strides (2, 2, 4, 4, then a 4 x 4 convolution) need a patch "
+                             "of at least %d" % (args.loss, args.patch_size, min_side(args.kernel_size)))
     if not (math.isfinite(args.patch_noise_sigma) and args.patch_noise_sigma >= 0):
         raise SystemExit("--patch_noise_sigma %g: needs a finite level of at least 0 (0: no noise)" % args.patch_noise_sigma)
     if "coco" not in args.dataset:
@@ -149,6 +198,18 @@ def seed_epoch(seed, epoch, rank=0):
     random.seed(s)
     np.random.seed(s)
     torch.manual_seed(s)
+
+
+class AdvNet(nn.Module):
+    """The discriminator behind `discriminator_forward`, as a module so that DistributedDataParallel sees the forward."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    def forward(self, x):
+        from .models.deblur_adversarial import discriminator_forward
+        return discriminator_forward(self.model, x)
 
 
 class TrainNet(nn.Module):
@@ -209,6 +270,17 @@ class Trainer(object):
         self.net = TrainNet(bare)
         if getattr(args, "distributed", False):
             self.net = torch.nn.parallel.DistributedDataParallel(self.net, device_ids=[args.gpu] if device.type == "cuda" else None)
+        self.loss_weights = parse_loss(args.loss)
+        self.bare_d = self.net_d = self.optimizer_d = self.scheduler_d = self.last_adv = None
+        if "ADV" in self.loss_weights:
+            # after G, so that G's initial weights are those of a run without ADV
+            from .models.deblur_adversarial import Discriminator
+            self.bare_d = Discriminator(n_feats=args.n_feats, kernel_size=args.kernel_size).to(device)
+            if device.type == "cuda":
+                self.bare_d = self.bare_d.to(memory_format=torch.channels_last)
+            self.net_d = AdvNet(self.bare_d)
+            if getattr(args, "distributed", False):
+                self.net_d = torch.nn.parallel.DistributedDataParallel(self.net_d, device_ids=[args.gpu] if device.type == "cuda" else None)
         self.scaler = None
         if args.amp:
             # fused: the scaler hands found_inf and the scale to the optimizer's kernel (`_step_supports_amp_scaling`); any other Adam
@@ -218,6 +290,11 @@ class Trainer(object):
         else:
             self.optimizer = torch.optim.Adam(bare.parameters(), lr=args.lr, betas=(0.9, 0.999))
         self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=args.lr_steps, gamma=args.lr_gamma)
+        if self.bare_d is not None:
+            # G's lr, betas and fusedness; a schedule of its own on the same milestones
+            fused = dict(fused=True) if args.amp else {}
+            self.optimizer_d = torch.optim.Adam(self.bare_d.parameters(), lr=args.lr, betas=(0.9, 0.999), **fused)
+            self.scheduler_d = torch.optim.lr_scheduler.MultiStepLR(self.optimizer_d, milestones=args.lr_steps, gamma=args.lr_gamma)
         self.jpeg = None
         if args.add_jpeg_artefacts:
             from .engine_blur_estimator import _jpeg
@@ -247,7 +324,12 @@ class Trainer(object):
             inputs = DT.patch_levels(DT.gather_patches(blurred, draws, ps), self.args.n_scales, torch.float16 if amp else torch.float32)
             targets = DT.patch_levels(DT.gather_patches(sharp, draws, ps), self.args.n_scales)
         outputs = list(self.net(*inputs))
+        if self.bare_d is not None:
+            return self._step_adversarial(outputs, targets, amp)
         loss = DT.pyramid_l1_loss([o.float() for o in outputs] if amp else outputs, targets)
+        w = self.loss_weights["L1"]
+        if w != 1.0:
+            loss = loss * w
         self.optimizer.zero_grad(set_to_none=True)
         if amp:
             self.scaler.scale(loss).backward()
@@ -257,6 +339,45 @@ class Trainer(object):
             loss.backward()
             self.optimizer.step()
         return loss.detach()
+
+    def _step_adversarial(self, outputs, targets, amp):
+        """The rest of a step with ADV in --loss (the module docstring, "One step with ADV"): the D update on the detached fake, then the
+        G update through the unwrapped discriminator with its parameters' requires_grad off.  `last_adv`: (loss_g, loss_d, the unweighted L1
+        term -- a zero where --loss has none), on the device."""
+        from .models import deblur_adversarial as DA
+        from .models import deblur_train as DT
+        fake = (outputs[0] + 127.5).contiguous(memory_format=torch.channels_last)
+        real = targets[0][:, :3] + 127.5
+        real = (real.half() if amp else real).contiguous(memory_format=torch.channels_last)
+        self.optimizer_d.zero_grad(set_to_none=True)
+        loss_d = DA.discriminator_loss(self.net_d, fake, real)
+        if amp:
+            self.scaler.scale(loss_d).backward()
+            self.scaler.step(self.optimizer_d)
+        else:
+            loss_d.backward()
+            self.optimizer_d.step()
+        for p in self.bare_d.parameters():
+            p.requires_grad_(False)
+        try:
+            loss_g = DA.adv_bce(DA.discriminator_forward(self.bare_d, fake).float(), 1)
+            total, l1 = self.loss_weights["ADV"] * loss_g, None
+            if "L1" in self.loss_weights:
+                l1 = DT.pyramid_l1_loss([o.float() for o in outputs] if amp else outputs, targets)
+                total = total + self.loss_weights["L1"] * l1
+            self.optimizer.zero_grad(set_to_none=True)
+            if amp:
+                self.scaler.scale(total).backward()
+                self.scaler.step(self.optimizer)
+                self.scaler.update()
+            else:
+                total.backward()
+                self.optimizer.step()
+        finally:
+            for p in self.bare_d.parameters():
+                p.requires_grad_(True)
+        self.last_adv = (loss_g.detach(), loss_d.detach(), l1.detach() if l1 is not None else torch.zeros_like(total))
+        return total.detach()
 
 
 def _epoch_of(name):
@@ -282,8 +403,14 @@ def save(trainer, args, epoch):
         utils.mkdir(models_dir)
         utils.mkdir(optim_dir)
         warn_if_not_picked(models_dir, epoch)
-    utils.save_on_master({"G": trainer.bare.state_dict()}, os.path.join(models_dir, "model-%d.pt" % epoch))
+    model = {"G": trainer.bare.state_dict()}
+    if trainer.bare_d is not None:
+        model["D"] = trainer.bare_d.state_dict()      # the reference's layout (model.py: Model.state_dict)
+    utils.save_on_master(model, os.path.join(models_dir, "model-%d.pt" % epoch))
     state = {"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.scheduler.state_dict(), "epoch": epoch, "args": vars(args)}
+    if trainer.bare_d is not None:
+        state["optimizer_D"] = trainer.optimizer_d.state_dict()
+        state["lr_scheduler_D"] = trainer.scheduler_d.state_dict()
     if trainer.scaler is not None:
         state["scaler"] = trainer.scaler.state_dict()
     utils.save_on_master(state, os.path.join(optim_dir, "optim-%d.pt" % epoch))
@@ -304,8 +431,17 @@ def resume(trainer, args):
         raise SystemExit("--resume: %s was written %s --amp and this run is %s it: the optimizer state (and the loss scale) of one does "
                          "not continue the other; %s the flag" % (path, "with" if was_amp else "without", "with" if args.amp else "without",
                                                                   "add" if was_amp else "drop"))
+    was_loss = ck.get("args", {}).get("loss", DEFAULT_LOSS)
+    if parse_loss(was_loss) != parse_loss(args.loss):
+        raise SystemExit("--resume: %s was written with --loss %s and this run is with --loss %s: the optimizer state (and the "
+                         "discriminator) of one does not continue the other; give --loss %s" % (path, was_loss, args.loss, was_loss))
     model_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "models", "model-%d.pt" % ck["epoch"])
-    trainer.bare.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True)["G"], strict=True)
+    model = torch.load(model_path, map_location="cpu", weights_only=True)
+    trainer.bare.load_state_dict(model["G"], strict=True)
+    if trainer.bare_d is not None:
+        trainer.bare_d.load_state_dict(model["D"], strict=True)
+        trainer.optimizer_d.load_state_dict(ck["optimizer_D"])
+        trainer.scheduler_d.load_state_dict(ck["lr_scheduler_D"])
     trainer.optimizer.load_state_dict(ck["optimizer"])
     trainer.scheduler.load_state_dict(ck["lr_scheduler"])
     if trainer.scaler is not None:
@@ -408,22 +544,35 @@ def main(argv=None):
             loss = trainer.step(images_CPU, blur_dicts)
             seen += len(images_CPU)
             if loss is not None and it % args.print_freq == 0:
-                value = loss.item()                  # the only read of the step's result: every --print_freq steps
+                adv = trainer.last_adv
+                if adv is None:
+                    value = loss.item()              # the only read of the step's result: every --print_freq steps
+                else:
+                    value, adv_g, adv_d, l1 = torch.stack((loss,) + adv).tolist()      # ... with ADV: the scalars in one read
                 line = "Epoch: [%d]  [%d/%d]  loss: %.4f  lr: %.6g  path: %s" % (epoch + 1, it, len(loader), value,
                                                                                   trainer.optimizer.param_groups[0]["lr"], trainer.bare.last_path)
+                if adv is not None:
+                    line += "  adv: %.4f  d: %.4f  d_path: %s" % (adv_g, adv_d, trainer.bare_d.last_path)
                 if trainer.scaler is not None:
                     line += "  scale: %g" % trainer.scaler.get_scale()      # a read of the device, like the loss's: only here
                 print(line)
                 if writer is not None:
                     step = it + epoch * len(loader)
-                    writer.add_scalar("losses/l1_pyramid", value, step)
+                    # the printed loss is the weighted total; this tag holds the L1 term itself, unweighted, with or without ADV
+                    if "L1" in trainer.loss_weights:
+                        writer.add_scalar("losses/l1_pyramid", value / trainer.loss_weights["L1"] if adv is None else l1, step)
+                    if adv is not None:
+                        writer.add_scalar("losses/adv_g", adv_g, step)
+                        writer.add_scalar("losses/adv_d", adv_d, step)
                     writer.add_scalar("learningRate", trainer.optimizer.param_groups[0]["lr"], step)
-                if not math.isfinite(value):
-                    raise SystemExit("Loss is %r, stopping training" % value)
+                if not all(math.isfinite(v) for v in ((value,) if adv is None else (value, adv_g, adv_d))):
+                    raise SystemExit("Loss is %r, stopping training" % (value if adv is None else (value, adv_g, adv_d),))
             it += 1
             if args.early_stop is not None and it > args.early_stop:
                 break
         trainer.scheduler.step()
+        if trainer.scheduler_d is not None:
+            trainer.scheduler_d.step()
         print("Epoch: [%d] done: %d steps, %d images, %d left out (a side below --patch_size %d), %.1f s"
               % (epoch + 1, it, seen, trainer.dropped, args.patch_size, time.time() - t0))
         if args.output_dir and ((epoch + 1) % args.save_every == 0 or epoch + 1 == args.epochs):

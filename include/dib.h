@@ -850,6 +850,38 @@ size_t dib_l1_pyramid_loss_workspace_bytes(long long n_pix);
 int dib_l1_pyramid_loss(const float *out_dev, const float *target_dev, int target_stride, long long n_pix, float gscale,
                         float *grad_dev, float *loss_dev, void *work_dev, void *stream);
 
+/* ADVERSARIAL LOSS of the DeepDeblur trainer (`train_deblurrer.py --loss 1*L1+1*ADV`, models/deblur_adversarial.py;
+ * csrc/dib_deblur_adv.hip).
+ *
+ * LeakyReLU in place on a convolution output of n_elems fp32 (dib_leaky_relu_mask) or IEEE Half (dib_leaky_relu_mask_f16, raw 16-bit
+ * words; upcast, multiplied in fp32, rounded once) elements:
+ *     x[i] = x[i] > 0 ? x[i] : x[i] * slope            NaN stays NaN; -0 stays -0 in fp32 and becomes +0 in the Half form, which
+ *                                                        is what torch's Half kernel gives on gfx950 (csrc/dib_deblur_adv.hip, `leak`)
+ *     mask[i / lane] bit (i % lane) = stored x[i] > 0    lane = 4 (fp32) / 8 (Half): dib_bias_act_mask_nhwc's layout; mask_dev may be NULL
+ * and its backward from that mask (out_dev may alias grad_dev):
+ *     out[i] = bit ? grad[i] : grad[i] * slope           Half: rounded once, and a -0 product becomes +0 as above
+ * One launch each.  DIB_EINVAL, before any launch: slope not finite or <= 0 (only for slope > 0 is the mask of the result the mask
+ * of the input); n_elems negative or no multiple of the lane; a null pointer (the forward's mask apart); x_dev / grad_dev / out_dev
+ * not 16-byte aligned.  n_elems == 0: DIB_OK, nothing is launched. */
+int dib_leaky_relu_mask(float *x_dev, long long n_elems, float slope, unsigned char *mask_dev, void *stream);
+int dib_leaky_relu_mask_f16(void *x_dev, long long n_elems, float slope, unsigned char *mask_dev, void *stream);
+int dib_leaky_relu_mask_backward(const float *grad_dev, const unsigned char *mask_dev, float slope, float *out_dev, long long n_elems,
+                                 void *stream);
+int dib_leaky_relu_mask_backward_f16(const void *grad_dev, const unsigned char *mask_dev, float slope, void *out_dev, long long n_elems,
+                                     void *stream);
+
+/* Binary cross-entropy with logits of n fp32 logits against a CONSTANT label (real_label 1: "real", 0: "fake"), mean over n.  With
+ * z = -x for label 1 and z = x for label 0, e = exp(-|z|):
+ *     *loss_dev  += (sum of max(z, 0) + log1p(e)) / float(n)                   ADDED: the caller zeroes it before the first call
+ *     grad_dev[i] = (label 1: -1, label 0: +1) * (gscale / float(n)) * sigma(z)  sigma(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e)
+ * A NaN logit gives a NaN at its own gradient element and a NaN loss, nothing else.  +-inf follows the formulas (z = +inf: term inf,
+ * sigma 1; z = -inf: term 0, sigma 0), where torch's binary_cross_entropy_with_logits gives NaN.  Two launches; the sum is taken in
+ * dib_l1_pyramid_loss's order, fixed by n alone (csrc/dib_deblur_adv.hip states it with its depth).  work_dev:
+ * dib_adv_bce_loss_workspace_bytes(n) bytes.  DIB_EINVAL: n < 1 or > 2^40, real_label not 0 or 1, null / misaligned (4 bytes) pointer. */
+size_t dib_adv_bce_loss_workspace_bytes(long long n);
+int dib_adv_bce_loss(const float *logits_dev, long long n, int real_label, float gscale, float *grad_dev, float *loss_dev, void *work_dev,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
