@@ -207,7 +207,10 @@ class RoIHeads(nn.Module):
         class-major from one kernel, every class's candidates sorted by one top-k launch, ONE batched NMS over the classes as
         independent sets -- on boxes moved apart by class * (largest coordinate + 1), the arithmetic of torchvision's batched_nms, so
         the same pairs suppress each other --, and the classes' survivors (at most detections_per_img of each can matter) ranked by
-        a last top-k.  Equal scores come out in (class, rank) order; the tensor form below leaves their order to an unstable sort."""
+        a last top-k.  Equal scores come out in (class, rank) order: within a class the lower RoI index first (it is also the one
+        that suppresses an equal-scored neighbour), across classes the lower label first, so of more than detections_per_img equal
+        scores the lowest classes' lowest ranks are the ones reported (tests/test_selection_gpu.py); the tensor form above leaves
+        their order to an unstable sort."""
         R, C = class_logits.shape
         dev, D = class_logits.device, self.detections_per_img
         if R == 0:

@@ -157,7 +157,9 @@ class RegionProposalNetwork(nn.Module):
         sets of <= pre-NMS-top-n boxes, already sorted by the per-level top-k, instead of N sets of their sum: the greedy pass,
         sequential in blocks of 64 boxes, is 4 x shorter (32 instead of 138 block steps at the training sizes) and the
         suppression mask has 4 x fewer words.  The survivors of all levels are then ranked by score (top-k), which is the
-        order batched_nms returns."""
+        order batched_nms returns.  On the kernels' path equal scores come out in (level, rank) order -- within a level the lower
+        anchor index first, across levels the lower level first, and of a run of equal scores across the last place the first
+        in that order are kept (tests/test_selection_gpu.py); the tensor path leaves their order to torch.topk."""
         N, L = proposals.shape[0], len(counts)
         objectness = objectness.detach().reshape(N, -1)
         K = max(min(self._n(self._pre), n) for n in counts)

@@ -340,7 +340,12 @@ int dib_bias_act_transpose(const float *in_dev, const float *bias_dev, float *ou
  * -inf), their level-relative indices into out_index_dev (optional).  With boxes_dev ([N][row_stride][4], same indexing): the
  * winners' boxes into out_boxes_dev [N][L][K][4], clipped to clip_wh_dev[n] = (width, height) when that is given, and
  * out_valid_dev [N][L][K] = score > -inf and both clipped sides >= min_size.  L <= 32.  (A long row is bound by the one compute unit
- * that sweeps it: callers split it into consecutive levels and merge the winners with a second call -- the order is the same.) */
+ * that sweeps it: callers split it into consecutive levels and merge the winners with a second call -- the order is the same.)
+ * The order, pinned by tests/test_selection_gpu.py against a stable sort: -0 and +0 are equal scores (each keeps its sign in
+ * out_scores_dev); denormals are numbers, above or below the zeros and never equal to them; NaN comes first, above +inf; equal
+ * scores -- the zeros, NaNs among themselves, -inf when a level has fewer than level_k[l] numbers -- come out in ascending
+ * level-relative index order, and when a run of equal scores straddles place level_k[l], its lowest indices are the ones taken.
+ * Only columns level_offset[0] .. level_offset[L] of a row are read (level_offset[0] may be > 0, row_stride beyond the last level). */
 int dib_topk_levels(const float *values_dev, long long row_stride, int N, const int *level_offset, const int *level_k, int L, int K,
                     const float *boxes_dev, const float *clip_wh_dev, float min_size, float *out_scores_dev, long long *out_index_dev,
                     float *out_boxes_dev, unsigned char *out_valid_dev, void *stream);
