@@ -576,15 +576,27 @@ def jpeg_roundtrip(image, q_luma, q_chroma):
     return out
 
 
+def check_trajectory_in_canvas(traj, canvas):
+    """The reference's IndexError for a host trajectory: a sample whose floor(re) or floor(im) reaches canvas - 1 splats on row or
+    column `canvas` (generate_PSF.py:59-75), whatever its exposure weight -- as dib_psf_fit refuses it.  floor(x) >= canvas - 1 is
+    x >= canvas - 1 for an integer canvas; one pass over the host data, nothing touches the device."""
+    if traj.numel() and bool((torch.view_as_real(traj) >= canvas - 1).any()):
+        raise IndexError("trajectory leaves the %d x %d canvas" % (canvas, canvas))
+
+
 def rasterize_psfs(traj, fractions, canvas=256, center=True, out_n=None, want64=True, want16=True):
     """traj: [B, iters] complex128 CUDA tensor (or anything torch.as_tensor accepts);
     fractions: B python floats.  Returns (psf64 [B,n,n] float64 | None, psf16 [B,n,n] float16 | None).
-    generate_PSF.py:31-83 + :106-123 + transforms.py:334-335 + engine.py:84 in two launches."""
+    generate_PSF.py:31-83 + :106-123 + transforms.py:334-335 + engine.py:84 in two launches.
+    A trajectory that arrives on the host and leaves the canvas on the high side raises IndexError before the upload, as the
+    reference and PSF.fit do; a device-resident one cannot be checked without a synchronisation and follows the border rule of
+    include/dib.h (the splats on row / column `canvas` are dropped)."""
     import ctypes
     traj = torch.as_tensor(traj)
     if traj.dtype != torch.complex128:
         raise TypeError("trajectory must be complex128")
     if not traj.is_cuda:
+        check_trajectory_in_canvas(traj, canvas)
         traj = traj.cuda(non_blocking=True)
     traj = traj.contiguous()
     if traj.dim() == 1:

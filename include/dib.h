@@ -263,6 +263,17 @@ int dib_clamp_boxes(float *boxes_dev, int N, int H, int W, void *stream);
  * psf64_dev: [B][out_n][out_n] float64 (may be NULL); psf16_dev: same shape, float16 converted
  * as torch.HalfTensor(ndarray) does (float64 -> float32 -> float16; engine.py:84) (may be NULL).
  * workspace_dev: dib_psf_rasterize_workspace_bytes(B, iters, canvas) bytes.
+ * Canvas border.  Low side: a coordinate below 1 (negative ones included) is clamped to cell 1
+ * as the reference clamps it (:59, :61), and splats there with its (vanishing) triangle weights.
+ * High side: a sample with floor(coord) >= canvas - 1 on either axis contributes only the cells
+ * inside the canvas -- its splats on row or column `canvas` are dropped, and one further out
+ * contributes nothing; the reference raises IndexError there (its accumulator has no such row),
+ * whatever the sample's exposure weight, and so does the host path (dib_psf_fit returns -2).  A
+ * kernel cannot raise without a synchronisation, so a caller that holds the trajectory on the
+ * host checks it before the upload (blur_ops.rasterize_psfs does); device-resident input
+ * follows the rule above.
+ * B == 0 is DIB_OK and launches nothing; canvas outside {64, 128, 256}, any other out_n,
+ * iters <= 0, B < 0, or a null traj_dev / fraction / workspace_dev with B > 0 is DIB_EINVAL.
  * ------------------------------------------------------------------------------------- */
 size_t dib_psf_rasterize_workspace_bytes(int B, int iters, int canvas);
 int dib_psf_rasterize(const double *traj_dev, int B, int iters, const double *fraction, int canvas,
