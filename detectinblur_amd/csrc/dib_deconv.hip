@@ -24,6 +24,7 @@
 #include <hip/hip_fp16.h>
 
 #include "dib_common.h"
+#include "dib_deconv_tv.h"
 
 namespace dib {
 namespace {
@@ -159,25 +160,28 @@ int rl_launch(const S *src, const E *epi, float *out, int C, int H, int W, const
 
 using namespace dib;
 
-extern "C" int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
-                                 int psf_dtype, int K, int iterations, float eps, void *stream) {
-  if (!y_dev || !out_dev || !work_dev || !table_dev) { set_error("dib_rl_deconvolve: null pointer"); return DIB_EINVAL; }
-  if (dtype != DIB_F16 && dtype != DIB_F32) { set_error("dib_rl_deconvolve: unknown image dtype %d", dtype); return DIB_EINVAL; }
-  if (psf_dtype != DIB_F16 && psf_dtype != DIB_F32) { set_error("dib_rl_deconvolve: unknown PSF dtype %d", psf_dtype); return DIB_EINVAL; }
-  if (K != 128 && K != 256) { set_error("dib_rl_deconvolve: K must be 128 or 256, got %d", K); return DIB_EINVAL; }
-  if (C <= 0 || H <= 0 || W <= 0) { set_error("dib_rl_deconvolve: empty shape %d x %d x %d", C, H, W); return DIB_EINVAL; }
-  if (iterations < 1 || iterations > 1000) { set_error("dib_rl_deconvolve: iterations must lie in 1..1000, got %d", iterations); return DIB_EINVAL; }
-  if (!(eps > 0.f)) { set_error("dib_rl_deconvolve: eps must be positive, got %g", (double)eps); return DIB_EINVAL; }
+namespace {
+
+// The refusals of both entries (`who` names the caller in the message); work_planes: the planes of C H W floats in work_dev
+int rl_check(const char *who, const void *y_dev, int dtype, const float *out_dev, const float *work_dev, int C, int H, int W, const void *table_dev,
+             int psf_dtype, int K, int iterations, float eps, int work_planes) {
+  if (!y_dev || !out_dev || !work_dev || !table_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
+  if (dtype != DIB_F16 && dtype != DIB_F32) { set_error("%s: unknown image dtype %d", who, dtype); return DIB_EINVAL; }
+  if (psf_dtype != DIB_F16 && psf_dtype != DIB_F32) { set_error("%s: unknown PSF dtype %d", who, psf_dtype); return DIB_EINVAL; }
+  if (K != 128 && K != 256) { set_error("%s: K must be 128 or 256, got %d", who, K); return DIB_EINVAL; }
+  if (C <= 0 || H <= 0 || W <= 0) { set_error("%s: empty shape %d x %d x %d", who, C, H, W); return DIB_EINVAL; }
+  if (iterations < 1 || iterations > 1000) { set_error("%s: iterations must lie in 1..1000, got %d", who, iterations); return DIB_EINVAL; }
+  if (!(eps > 0.f)) { set_error("%s: eps must be positive, got %g", who, (double)eps); return DIB_EINVAL; }
   const long long n = (long long)C * H * W;
   if (n >= 0x7fffffffll || C > 65535 || (H + RL_TH - 1) / RL_TH > 65535) {
-    set_error("dib_rl_deconvolve: image %d x %d x %d is too large", C, H, W);
+    set_error("%s: image %d x %d x %d is too large", who, C, H, W);
     return DIB_ESHAPE;
   }
   {   // the three buffers are read and written in turn: none may overlap another
     const uintptr_t y = (uintptr_t)y_dev, o = (uintptr_t)out_dev, w = (uintptr_t)work_dev;
-    const uintptr_t yb = (uintptr_t)n * (dtype == DIB_F16 ? 2 : 4), ob = (uintptr_t)n * 4, wb = (uintptr_t)n * 8;
+    const uintptr_t yb = (uintptr_t)n * (dtype == DIB_F16 ? 2 : 4), ob = (uintptr_t)n * 4, wb = (uintptr_t)n * 4 * work_planes;
     if ((y < o + ob && o < y + yb) || (y < w + wb && w < y + yb) || (o < w + wb && w < o + ob)) {
-      set_error("dib_rl_deconvolve: y_dev, out_dev and work_dev must not overlap");
+      set_error("%s: y_dev, out_dev and work_dev must not overlap", who);
       return DIB_EINVAL;
     }
   }
@@ -186,27 +190,61 @@ extern "C" int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, f
     set_error("Padding size should be less than the corresponding input dimension (image is %dx%d)", H, W);
     return DIB_ESHAPE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int *tab = (const int *)table_dev;
-  const int pf = psf_dtype == DIB_F16 ? 1 : 0;
-  float *q = work_dev, *spare = work_dev + n;
+  return DIB_OK;
+}
+
+// The iteration of both entries.  xg == nullptr: x_{k+1} = clamp(x_k * A* q, 0, 1), two launches per iteration.  Otherwise xg is a
+// third plane and x_{k+1} = clamp((x_k * g_k) * A* q, 0, 1): csrc/dib_deconv_tv.hip writes x_k * g_k there and sweep A* takes it as
+// its epi plane, three launches per iteration.
+int rl_iterate(const void *y_dev, int dtype, float *out_dev, float *q, float *spare, float *xg, int C, int H, int W, const int *tab, int pf,
+               int K, int iterations, float eps, float tv_lambda, float tv_beta, hipStream_t s) {
   const __half *y16 = (const __half *)y_dev;
   const float *y32 = (const float *)y_dev;
   const float *x = nullptr;      // x_k for k >= 1 (x_0 = y itself, in its own type)
   for (int k = 0; k < iterations; ++k) {
     float *next = ((iterations - 1 - k) & 1) ? spare : out_dev;      // x_N lands in out_dev, x_{N-1} in the spare plane, ...
     int rc;
+    if (xg) {
+      rc = x ? tv_weight_launch(x, DIB_F32, xg, C, H, W, tv_lambda, tv_beta, s) : tv_weight_launch(y_dev, dtype, xg, C, H, W, tv_lambda, tv_beta, s);
+      if (rc) return rc;
+    }
     if (dtype == DIB_F16) {
       rc = x ? rl_launch<false>(x, y16, q, C, H, W, tab, K, pf, eps, s) : rl_launch<false>(y16, y16, q, C, H, W, tab, K, pf, eps, s);
       if (rc) return rc;
-      rc = x ? rl_launch<true>((const float *)q, x, next, C, H, W, tab, K, pf, eps, s) : rl_launch<true>((const float *)q, y16, next, C, H, W, tab, K, pf, eps, s);
+      if (xg) rc = rl_launch<true>((const float *)q, (const float *)xg, next, C, H, W, tab, K, pf, eps, s);
+      else rc = x ? rl_launch<true>((const float *)q, x, next, C, H, W, tab, K, pf, eps, s) : rl_launch<true>((const float *)q, y16, next, C, H, W, tab, K, pf, eps, s);
     } else {
       rc = rl_launch<false>(x ? x : y32, y32, q, C, H, W, tab, K, pf, eps, s);
       if (rc) return rc;
-      rc = rl_launch<true>((const float *)q, x ? x : y32, next, C, H, W, tab, K, pf, eps, s);
+      rc = rl_launch<true>((const float *)q, xg ? (const float *)xg : (x ? x : y32), next, C, H, W, tab, K, pf, eps, s);
     }
     if (rc) return rc;
     x = next;
   }
   return DIB_OK;
+}
+
+}  // namespace
+
+extern "C" int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
+                                 int psf_dtype, int K, int iterations, float eps, void *stream) {
+  const int rc = rl_check("dib_rl_deconvolve", y_dev, dtype, out_dev, work_dev, C, H, W, table_dev, psf_dtype, K, iterations, eps, 2);
+  if (rc) return rc;
+  const size_t n = (size_t)C * H * W;
+  return rl_iterate(y_dev, dtype, out_dev, work_dev, work_dev + n, nullptr, C, H, W, (const int *)table_dev, psf_dtype == DIB_F16 ? 1 : 0, K,
+                    iterations, eps, 0.f, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int dib_rl_deconvolve_tv(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
+                                    int psf_dtype, int K, int iterations, float eps, float tv_lambda, float tv_beta, void *stream) {
+  const int rc = rl_check("dib_rl_deconvolve_tv", y_dev, dtype, out_dev, work_dev, C, H, W, table_dev, psf_dtype, K, iterations, eps, 3);
+  if (rc) return rc;
+  if (!tv_params_ok(tv_lambda, tv_beta)) {
+    set_error("dib_rl_deconvolve_tv: tv_lambda must lie in (0, 0.1] and tv_beta be positive and finite, got %g and %g", (double)tv_lambda,
+              (double)tv_beta);
+    return DIB_EINVAL;
+  }
+  const size_t n = (size_t)C * H * W;
+  return rl_iterate(y_dev, dtype, out_dev, work_dev, work_dev + n, work_dev + 2 * n, C, H, W, (const int *)table_dev, psf_dtype == DIB_F16 ? 1 : 0,
+                    K, iterations, eps, tv_lambda, tv_beta, (hipStream_t)stream);
 }

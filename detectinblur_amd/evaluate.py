@@ -16,7 +16,8 @@ detector a Half image; `--amp` is independent of it and leaves the deblurrer alo
 `--acclimate_norm` (this repo's flag for the reference layer's `acclimation_mode`, models/batchnorm.py:142-157, and the helpers of
 its utils.py:80-217): online batch-norm statistics, updated on the device image by image (models/batchnorm.py, engine.evaluate).
 `--deconvolve_first` (this repo): Richardson-Lucy deconvolution with the image's own, known PSF in front of the detector in every sweep
-cell (models/deconvolve.py; `--deconvolve_iterations N`): the non-blind upper bound next to `--deblur_first`'s blind baseline."""
+cell (models/deconvolve.py; `--deconvolve_iterations N`): the non-blind upper bound next to `--deblur_first`'s blind baseline.
+`--deconvolve_tv LAMBDA` (this repo) adds the total-variation prior of Dey et al. 2006 to every iteration (beta = 1e-2)."""
 import os
 import argparse
 
@@ -35,6 +36,7 @@ SWEEP_PARAMS = [0.005, 0.001, 0.00005]
 SWEEP_FRACTIONS = [1 / 25, 1 / 10, 1 / 5, 1 / 2, 1]
 ACCLIMATION_PRIOR = 16
 DECONVOLVE_ITERATIONS, MAX_DECONVOLVE_ITERATIONS = 30, 1000      # models/deconvolve.py's DEFAULT_ITERATIONS / MAX_ITERATIONS
+MAX_DECONVOLVE_TV, DECONVOLVE_TV_BETA = 0.1, 1e-2                # models/deconvolve.py's MAX_TV_LAMBDA / DEFAULT_TV_BETA
 
 
 def build_parser():
@@ -72,6 +74,10 @@ def build_parser():
     p.add_argument("--deconvolve_iterations", type=int, default=DECONVOLVE_ITERATIONS, metavar="N", action=_StoreGiven, help="(this repo) with --deconvolve_first: "
                    "Richardson-Lucy iterations, 1..%d (default %d); more sharpen further and amplify noise and JPEG residue further"
                    % (MAX_DECONVOLVE_ITERATIONS, DECONVOLVE_ITERATIONS))
+    p.add_argument("--deconvolve_tv", type=float, default=None, metavar="LAMBDA", help="(this repo) with --deconvolve_first: total-variation "
+                   "regularised Richardson-Lucy (Dey et al. 2006), one factor per pixel and iteration that keeps the iteration from "
+                   "amplifying noise, block and JPEG residue.  LAMBDA in (0, %g]; 0.002 to 0.01 is the working range, larger values "
+                   "flatten detail.  beta is 1e-2.  Unset: the plain iteration" % MAX_DECONVOLVE_TV)
     p.add_argument("--restoration_metrics", action="store_true", help="(this repo) Per sweep cell, PSNR and SSIM of the blurred image and "
                    "of what --deblur_first / --deconvolve_first makes of it, against the image before the blur (quality.py; one HIP pass "
                    "per image, accumulated on the device).  Needs --gpu_blur.  No accuracy claim")
@@ -91,10 +97,13 @@ class _StoreGiven(argparse.Action):
 def reject_deconvolution_conflicts(args):
     """--deconvolve_first's refusals, before anything is built."""
     n = getattr(args, "deconvolve_iterations", DECONVOLVE_ITERATIONS)
+    tv = getattr(args, "deconvolve_tv", None)
     if not getattr(args, "deconvolve_first", False):
         if getattr(args, "deconvolve_iterations_given", False):
             raise SystemExit("--deconvolve_iterations needs --deconvolve_first: it is the iteration count of that stage and nothing else "
                              "reads it")
+        if tv is not None:
+            raise SystemExit("--deconvolve_tv needs --deconvolve_first: it is the prior of that stage's iteration and nothing else reads it")
         return
     if getattr(args, "deblur_first", False):
         raise SystemExit("--deconvolve_first with --deblur_first: both replace the image in front of the detector (the blind network "
@@ -107,6 +116,9 @@ def reject_deconvolution_conflicts(args):
                          "that forward model")
     if not (1 <= n <= MAX_DECONVOLVE_ITERATIONS):
         raise SystemExit("--deconvolve_iterations %d: the iteration count lies in 1..%d" % (n, MAX_DECONVOLVE_ITERATIONS))
+    if tv is not None and not (0 < tv <= MAX_DECONVOLVE_TV):
+        raise SystemExit("--deconvolve_tv %g: lambda lies in (0, %g] (0.002 to 0.01 is the working range; without the flag the iteration "
+                         "is the plain one)" % (tv, MAX_DECONVOLVE_TV))
 
 
 def reject_restoration_metrics_conflicts(args):
@@ -124,11 +136,13 @@ def reject_restoration_metrics_conflicts(args):
 
 
 def build_deconvolver(args):
-    """the Deconvolver of `--deconvolve_first` with `--deconvolve_iterations`, or None"""
+    """the Deconvolver of `--deconvolve_first` with `--deconvolve_iterations` and `--deconvolve_tv`, or None"""
     if not getattr(args, "deconvolve_first", False):
         return None
     from .models.deconvolve import Deconvolver
-    return Deconvolver(iterations=getattr(args, "deconvolve_iterations", DECONVOLVE_ITERATIONS))
+    tv = getattr(args, "deconvolve_tv", None)
+    return Deconvolver(iterations=getattr(args, "deconvolve_iterations", DECONVOLVE_ITERATIONS), tv_lambda=0.0 if tv is None else tv,
+                       tv_beta=DECONVOLVE_TV_BETA)
 
 
 def reject_acclimation_conflicts(args):

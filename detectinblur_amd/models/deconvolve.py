@@ -15,12 +15,27 @@ synchronisation, workspace from torch's allocator: capturable); CPU tensors take
 (gathers by precomputed index vectors), which is also what the HIP path is measured against on the GPU.
 
 No accuracy claim: synthetic data cannot show AP, and Richardson-Lucy amplifies whatever the forward model does not explain
-(--add_noise, --add_jpeg_artefacts residue) a little more with every iteration: that is what --deconvolve_iterations is for."""
+(--add_noise, --add_jpeg_artefacts residue) a little more with every iteration: that is what --deconvolve_iterations is for.
+
+The total-variation prior (`tv_lambda` > 0; evaluate.py --deconvolve_tv; Dey et al. 2006; include/dib.h, dib_tv_weight and
+dib_rl_deconvolve_tv; csrc/dib_deconv_tv.hip) is the other remedy: one factor per pixel and iteration from a 7-point stencil of x_k,
+    dx[i, j] = x[i, j + 1] - x[i, j] (0 in the last column)      dy[i, j] = x[i + 1, j] - x[i, j] (0 in the last row)
+    n = sqrt(dx^2 + dy^2 + beta^2);  p = dx / n;  r = dy / n;  div[i, j] = (p[i, j] - p[i, j - 1]) + (r[i, j] - r[i - 1, j])
+    g = 1 / (1 - lambda div);  x_{k+1} = clamp((x_k * g_k) * A* q, 0, 1)
+which pulls the estimate toward piecewise-constant images: what A does not explain is no longer amplified iteration after iteration.
+0 < lambda <= 0.1 (0.002 to 0.01 is the working range: larger values flatten detail), beta > 0 (1e-2: below that fp32 loses the
+conditioning of dx / n on near-flat regions).  `tv_weight_torch` is the op-for-op restatement of x * g, `tv_weight` takes the HIP
+entry for CUDA tensors (1 / n and g to 1 ulp there: the two agree to rounding); the HIP iteration is three launches and a 3-plane
+workspace.  tv_lambda = 0 is the plain iteration, call for call."""
+import math
+
 import torch
 
 PAD_REFLECT, PAD_ZERO, PAD_REPLICATE = 0, 1, 2
 DEFAULT_ITERATIONS = 30
 MAX_ITERATIONS = 1000
+DEFAULT_TV_BETA = 1e-2
+MAX_TV_LAMBDA = 0.1
 
 
 def pad_mode_for(K, H, W):
@@ -133,6 +148,63 @@ def _check(K, H, W, iterations, eps):
                            "image, so its forward model is not defined" % (H, W))
 
 
+def _check_tv(tv_lambda, tv_beta, who="richardson_lucy", needed=False):
+    """True when the total-variation factor is on (tv_lambda > 0); 0 is the plain iteration unless the factor itself is asked for"""
+    lam, beta = float(tv_lambda), float(tv_beta)
+    if not ((0 < lam <= MAX_TV_LAMBDA) or (lam == 0 and not needed)):
+        raise ValueError("%s: tv_lambda must lie in (0, %g]%s, got %r" % (who, MAX_TV_LAMBDA, "" if needed else " (or be 0: no prior)", tv_lambda))
+    if not (beta > 0 and math.isfinite(beta)):
+        raise ValueError("%s: tv_beta must be positive and finite, got %r" % (who, tv_beta))
+    return lam > 0
+
+
+def _f32(v):
+    """the fp32 rounding of a Python number, as a Python float"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _tv_weight(x, lam, b2):
+    """x * g of fp32 planes C x H x W, every operation in the order of include/dib.h; lam, b2: fp32 values of lambda and beta * beta"""
+    dx, dy = torch.zeros_like(x), torch.zeros_like(x)
+    dx[:, :, :-1] = x[:, :, 1:] - x[:, :, :-1]
+    dy[:, :-1, :] = x[:, 1:, :] - x[:, :-1, :]
+    n = torch.sqrt(dx * dx + dy * dy + b2)
+    p, r = dx / n, dy / n
+    p_left, r_up = torch.zeros_like(x), torch.zeros_like(x)
+    p_left[:, :, 1:] = p[:, :, :-1]
+    r_up[:, 1:, :] = r[:, :-1, :]
+    div = (p - p_left) + (r - r_up)
+    return x * (1.0 / (1.0 - lam * div))
+
+
+@torch.no_grad()
+def tv_weight_torch(x, tv_lambda, tv_beta=DEFAULT_TV_BETA):
+    """The total-variation factor applied: x * g (this module's docstring) in plain torch ops on x's device, fp32, of x's shape
+    (C x H x W or H x W; planes independent)."""
+    _check_tv(tv_lambda, tv_beta, "tv_weight", needed=True)
+    b = _f32(tv_beta)
+    return _tv_weight(_planar(x).float(), _f32(tv_lambda), _f32(b * b)).reshape(x.shape)
+
+
+@torch.no_grad()
+def tv_weight(x, tv_lambda, tv_beta=DEFAULT_TV_BETA):
+    """x * g: CUDA tensors (Half or fp32) take dib_tv_weight on the current stream, one launch, no synchronisation; CPU tensors the
+    torch restatement."""
+    if not x.is_cuda:
+        return tv_weight_torch(x, tv_lambda, tv_beta)
+    from .. import _lib, blur_ops
+    if x.dtype not in blur_ops._DT:
+        raise TypeError("tv_weight needs a float16 / float32 image")
+    _check_tv(tv_lambda, tv_beta, "tv_weight", needed=True)
+    v = _planar(x)
+    v = v if v.is_contiguous() else v.contiguous()
+    C, H, W = (int(s) for s in v.shape)
+    out = torch.empty((C, H, W), dtype=torch.float32, device=v.device)
+    _lib.check(_lib.lib().dib_tv_weight(v.data_ptr(), blur_ops._DT[v.dtype], out.data_ptr(), C, H, W, float(tv_lambda), float(tv_beta),
+                                        _lib.stream_of(v)))
+    return out.reshape(x.shape)
+
+
 def forward_blur(image, table_or_psf, adjoint=False):
     """A x (or A* x) in fp32 by the torch restatement, on the image's device."""
     taps = _as_taps(table_or_psf)
@@ -142,23 +214,27 @@ def forward_blur(image, table_or_psf, adjoint=False):
 
 
 @torch.no_grad()
-def richardson_lucy_torch(image, table_or_psf, iterations=DEFAULT_ITERATIONS, eps=1e-6):
-    """The iteration in plain torch ops on the image's device (CPU or GPU), fp32."""
+def richardson_lucy_torch(image, table_or_psf, iterations=DEFAULT_ITERATIONS, eps=1e-6, tv_lambda=0.0, tv_beta=DEFAULT_TV_BETA):
+    """The iteration in plain torch ops on the image's device (CPU or GPU), fp32; tv_lambda > 0: with the total-variation factor."""
     taps = _as_taps(table_or_psf)
     y = _planar(image).float()
     _check(taps.K, y.shape[1], y.shape[2], iterations, eps)
+    tv = _check_tv(tv_lambda, tv_beta)
+    lam, b = _f32(tv_lambda), _f32(tv_beta)
+    b2 = _f32(b * b)
     sweeps = _Sweeps(taps, y.shape[1], y.shape[2], y.device)
     x = y
     for _ in range(int(iterations)):
         q = y / sweeps.apply(x, False).clamp_min(eps)
-        x = (x * sweeps.apply(q, True)).clamp(0, 1)
+        x = ((_tv_weight(x, lam, b2) if tv else x) * sweeps.apply(q, True)).clamp(0, 1)
     return x.reshape(image.shape)
 
 
 @torch.no_grad()
-def richardson_lucy_hip(image, tables, index=0, iterations=DEFAULT_ITERATIONS, eps=1e-6):
+def richardson_lucy_hip(image, tables, index=0, iterations=DEFAULT_ITERATIONS, eps=1e-6, tv_lambda=0.0, tv_beta=DEFAULT_TV_BETA):
     """dib_rl_deconvolve on a CUDA image with table `index` of a blur_ops.TapTables (compacted with normalize=True), on the current
-    stream.  No synchronisation; the workspace (2 C H W floats) comes from torch's allocator."""
+    stream.  No synchronisation; the workspace (2 C H W floats) comes from torch's allocator.  tv_lambda > 0: dib_rl_deconvolve_tv,
+    with a workspace of 3 C H W floats."""
     from .. import _lib, blur_ops
     if not image.is_cuda or image.dtype not in blur_ops._DT:
         raise TypeError("richardson_lucy_hip needs a float16 / float32 CUDA image")
@@ -166,10 +242,17 @@ def richardson_lucy_hip(image, tables, index=0, iterations=DEFAULT_ITERATIONS, e
     y = y if y.is_contiguous() else y.contiguous()
     C, H, W = (int(v) for v in y.shape)
     _check(tables.K, H, W, iterations, eps)
+    tv = _check_tv(tv_lambda, tv_beta)
     if not 0 <= index < tables.count:
         raise ValueError("table index %d out of range (%d tables)" % (index, tables.count))
     blur_ops._await(tables)
     out = torch.empty((C, H, W), dtype=torch.float32, device=y.device)
+    if tv:
+        work = torch.empty((3, C, H, W), dtype=torch.float32, device=y.device)
+        _lib.check(_lib.lib().dib_rl_deconvolve_tv(y.data_ptr(), blur_ops._DT[y.dtype], out.data_ptr(), work.data_ptr(), C, H, W,
+                                                   tables.ptr(index), blur_ops._DT[getattr(tables, "dtype", torch.float16)], tables.K,
+                                                   int(iterations), float(eps), float(tv_lambda), float(tv_beta), _lib.stream_of(y)))
+        return out.reshape(image.shape)
     work = torch.empty((2, C, H, W), dtype=torch.float32, device=y.device)
     _lib.check(_lib.lib().dib_rl_deconvolve(y.data_ptr(), blur_ops._DT[y.dtype], out.data_ptr(), work.data_ptr(), C, H, W, tables.ptr(index),
                                             blur_ops._DT[getattr(tables, "dtype", torch.float16)], tables.K, int(iterations), float(eps),
@@ -177,13 +260,13 @@ def richardson_lucy_hip(image, tables, index=0, iterations=DEFAULT_ITERATIONS, e
     return out.reshape(image.shape)
 
 
-def richardson_lucy(image, table_or_psf, iterations=DEFAULT_ITERATIONS, eps=1e-6):
+def richardson_lucy(image, table_or_psf, iterations=DEFAULT_ITERATIONS, eps=1e-6, tv_lambda=0.0, tv_beta=DEFAULT_TV_BETA):
     """image: C x H x W (or H x W), Half or fp32, the blurred image.  table_or_psf: a blur_ops.TapTables (its first table), a
     (TapTables, index) pair, a K x K PSF tensor (un-normalised, as blur_dict["psf"]: divided by its sum in its own dtype, as the blur
     does) or a Taps.  Returns fp32 of the image's shape on its device.  CUDA images take the HIP entry (a PSF is compacted first); CPU
-    images the torch restatement."""
+    images the torch restatement.  tv_lambda > 0 (and tv_beta): the total-variation factor in every iteration; 0: the plain iteration."""
     if not image.is_cuda:
-        return richardson_lucy_torch(image, table_or_psf, iterations, eps)
+        return richardson_lucy_torch(image, table_or_psf, iterations, eps, tv_lambda, tv_beta)
     from .. import blur_ops
     if isinstance(table_or_psf, tuple):
         tables, index = table_or_psf
@@ -194,18 +277,20 @@ def richardson_lucy(image, table_or_psf, iterations=DEFAULT_ITERATIONS, eps=1e-6
     else:
         psf = torch.as_tensor(table_or_psf).to(image.device)
         tables, index = blur_ops.compact_psfs([psf], normalize=True), 0
-    return richardson_lucy_hip(image, tables, index, iterations, eps)
+    return richardson_lucy_hip(image, tables, index, iterations, eps, tv_lambda, tv_beta)
 
 
 class Deconvolver(object):
     """The --deconvolve_first stage: `deconvolve_(image, blur_dict, psf, tables)` mirrors models.deblur.Deblurer.deblur_."""
 
-    def __init__(self, iterations=DEFAULT_ITERATIONS, eps=1e-6):
+    def __init__(self, iterations=DEFAULT_ITERATIONS, eps=1e-6, tv_lambda=0.0, tv_beta=DEFAULT_TV_BETA):
         if not (1 <= int(iterations) <= MAX_ITERATIONS):
             raise ValueError("Deconvolver: iterations must lie in 1..%d, got %r" % (MAX_ITERATIONS, iterations))
         if not eps > 0:
             raise ValueError("Deconvolver: eps must be positive, got %r" % (eps,))
+        _check_tv(tv_lambda, tv_beta, "Deconvolver")
         self.iterations, self.eps = int(iterations), float(eps)
+        self.tv_lambda, self.tv_beta = float(tv_lambda), float(tv_beta)      # 0: the plain iteration
         self.calls = 0
 
     def deconvolve_(self, image, blur_dict, psf, tables=None, index=0):
@@ -218,5 +303,5 @@ class Deconvolver(object):
             return image
         self.calls += 1
         if image.is_cuda and tables is not None and tables.K == psf.shape[0] and not tables.large:
-            return richardson_lucy_hip(image, tables, index, self.iterations, self.eps)
-        return richardson_lucy(image, psf, self.iterations, self.eps)
+            return richardson_lucy_hip(image, tables, index, self.iterations, self.eps, self.tv_lambda, self.tv_beta)
+        return richardson_lucy(image, psf, self.iterations, self.eps, self.tv_lambda, self.tv_beta)

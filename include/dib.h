@@ -729,6 +729,36 @@ int dib_rl_deconvolve(const void *y_dev, int dtype, float *out_dev, float *work_
                       int psf_dtype, int K, int iterations, float eps, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Total-variation regularised Richardson-Lucy (Dey et al. 2006, "RL-TV"; this library's addition; `evaluate.py --deconvolve_tv`): one
+ * multiplicative factor per pixel and iteration in front of the plain update, which keeps the iteration from amplifying what A does
+ * not explain (noise, block and JPEG residue).  Per plane x of H x W, planes independent, with beta > 0 and 0 < lambda <= 0.1:
+ *     dx[i, j] = x[i, j + 1] - x[i, j]   (0 where j == W - 1)         dy[i, j] = x[i + 1, j] - x[i, j]   (0 where i == H - 1)
+ *     n[i, j]  = sqrt(dx^2 + dy^2 + beta^2)                            p = dx / n,   r = dy / n
+ *     div[i, j] = (p[i, j] - p[i, j - 1]) + (r[i, j] - r[i - 1, j])    with p[i, -1] = 0 and r[-1, j] = 0
+ *     g = 1 / (1 - lambda * div)                                       tv_weight(x) = x * g
+ *     q = y / max(A x_k, eps);   x_{k+1} = clamp((x_k * g_k) * (A* q), 0, 1);   x_0 = y
+ * |p|, |r| < 1, so |div| < 4 and the denominator lies in (0.6, 1.4): g is finite and positive for finite input.  A flat neighbourhood
+ * gives div = 0 and g = 1 exactly: black stays black, a constant stays constant, a 1 x 1 plane is returned unchanged.  The stencil is
+ * seven points of x_k -- the centre, its four neighbours, (i + 1, j - 1) and (i - 1, j + 1) -- and never leaves the plane.  All fp32,
+ * every sum, difference and product rounded on its own in the order written (the sum under the root as (dx dx + dy dy) + beta beta),
+ * x_0 = y read as fp32; 1 / n and g are computed to 1 ulp each (the hardware's reciprocal square root and reciprocal, exact at 1),
+ * p = dx (1 / n), r = dy (1 / n): the result agrees with an IEEE evaluation to rounding, not bit for bit.  A, A*, eps and the
+ * boundary rules of the two sweeps are dib_rl_deconvolve's.  (x_k * g_k) is rounded first and then multiplied by A* q: sweep A*
+ * runs as it is, with x_k * g_k as the plane its epilogue multiplies.
+ *
+ * dib_tv_weight: out_dev (fp32 C x H x W) = tv_weight of x_dev (`dtype`, C x H x W), one launch on `stream`, every pixel loaded and
+ * stored once.  DIB_EINVAL (nothing launched): null pointer, unknown dtype, C, H or W < 1, tv_lambda outside (0, 0.1], tv_beta not
+ * positive or not finite, overlapping buffers.  DIB_ESHAPE: C H W >= 2^31 - 1.
+ * dib_rl_deconvolve_tv: dib_rl_deconvolve with the factor.  work_dev: 3 C H W floats (q, the spare plane, x_k * g_k); three launches
+ * per iteration (the factor, sweep A, sweep A*); the result ends in out_dev for odd and even counts.  No allocation, no host
+ * synchronisation, no atomics: deterministic and capturable.  Refusals: dib_rl_deconvolve's, and DIB_EINVAL for tv_lambda and tv_beta
+ * as above.  dib_rl_deconvolve itself is unchanged: its launches, its 2-plane workspace, its bits.
+ * ------------------------------------------------------------------------------------- */
+int dib_tv_weight(const void *x_dev, int dtype, float *out_dev, int C, int H, int W, float tv_lambda, float tv_beta, void *stream);
+int dib_rl_deconvolve_tv(const void *y_dev, int dtype, float *out_dev, float *work_dev, int C, int H, int W, const void *table_dev,
+                         int psf_dtype, int K, int iterations, float eps, float tv_lambda, float tv_beta, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Restoration quality (this library's addition; quality.py, `train_deblurrer.py --validate_images`): how close image a is to image b.
  * a_dev, b_dev: planar C x H x W, contiguous, each DIB_F16 or DIB_F32 (any pairing), aligned to their element type only; L = data_range.
  * A stated reading (DeepDeblur reports PSNR and SSIM; its loss/ package is not in the reference tree): Wang et al. 2004 as
