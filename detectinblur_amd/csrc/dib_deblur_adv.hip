@@ -10,7 +10,7 @@
 //                            is what this path is held to bit for bit.
 //   (b) leaky_bwd_kernel     its backward from that mask: out = bit ? g : g * slope.  out may be g.  For slope > 0 the sign of the
 //                            result is the sign of the input, so the mask of the result serves (slope <= 0 is refused).
-//   (c) adv_bce_partial_kernel + adv_bce_final_kernel
+//   (c) sliced_sum_partial_kernel<BceTerm> + sliced_sum_final_kernel
 //                            binary cross-entropy with logits against a CONSTANT label (1: "real", 0: "fake"), mean over n, added into
 //                            a device scalar, with the gradient stored beside it.  With z = -x for label 1 and z = x for label 0:
 //                                term    = softplus(z) = max(z, 0) + log1p(exp(-|z|))
@@ -20,14 +20,10 @@
 //                            formulas: z = +inf gives term inf and sigma 1, z = -inf gives term 0 and sigma 0 (torch's
 //                            binary_cross_entropy_with_logits gives NaN there: not compared).
 //
-// THE SUMMATION ORDER of (c) is dib_l1_pyramid_loss's (csrc/dib_deblur_train.hip), fixed by n alone, so two calls on the same input
-// agree bit for bit: the n terms, in memory order, are cut into S = ceil(n / 2048) (capped at 1024) slices of consecutive elements, the
-// first n % S one element longer; lane t of a slice's workgroup of 256 adds the terms of elements slice_begin + t, + 256, ... one after
-// the other: a chain of L = ceil(slice length / 256); the 256 lanes are added as a tree of 8 levels in LDS (lane t takes lane t + h for
-// h = 128, 64, ..., 1); the second launch adds the S partial sums in slice order from slice 0, divides by float(n) and adds the result
-// onto the loss scalar.  DEPTH = L + 8 + S - 1 additions, then one division and one addition onto the scalar;
-// models/deblur_adversarial.py restates it as `adv_loss_depth`.
+// THE SUMMATION ORDER of (c), fixed by n alone, is the scalar losses' of dib_sliced_sum.h -- dib_l1_pyramid_loss's, by the same kernels;
+// models/deblur_adversarial.py restates its depth as `adv_loss_depth`.
 #include "dib_eltwise_vec.h"      // F32Lane, F16Lane (unpack, pack, sign_mask); args_ok, grid_1d, launch
+#include "dib_sliced_sum.h"
 #include <cmath>
 #include <type_traits>
 
@@ -97,47 +93,21 @@ static int leaky_backward(const char *who, const void *g, const unsigned char *m
 }
 
 // ---- (c) binary cross-entropy with logits against a constant label ----------------------------------------------------------------
-constexpr int ADV_THREADS = 256, ADV_MAX_SLICES = 1024, ADV_ELEMS_PER_LANE = 8;
-
-static int adv_slices(long long n) {
-  const long long per = (long long)ADV_THREADS * ADV_ELEMS_PER_LANE;
-  long long S = (n + per - 1) / per;
-  if (S > ADV_MAX_SLICES) S = ADV_MAX_SLICES;
-  return S < 1 ? 1 : (int)S;
-}
-
-__host__ __device__ inline long long adv_slice_begin(long long n, int S, int s) { return n / S * s + (n % S < s ? n % S : s); }
-
-__global__ __launch_bounds__(ADV_THREADS) void adv_bce_partial_kernel(const float *__restrict__ logits, long long n, int S, int real_label,
-                                                                     float k, float *__restrict__ grad, float *__restrict__ partial) {
-  __shared__ float sh[ADV_THREADS];
-  const int t = threadIdx.x, s = blockIdx.x;
-  const long long e1 = adv_slice_begin(n, S, s + 1);
-  const float ks = real_label ? -k : k;
-  float acc = 0.f;
-  for (long long i = adv_slice_begin(n, S, s) + t; i < e1; i += ADV_THREADS) {
+struct BceTerm {
+  const float *logits;
+  int real_label;
+  float k;
+  float *grad;
+  __device__ __forceinline__ float operator()(long long i) const {
+    const float ks = real_label ? -k : k;
     const float x = logits[i];
     const float z = real_label ? -x : x;
     const float e = expf(-fabsf(z));               // in (0, 1]; NaN for a NaN logit
     const float d = 1.f + e;
     grad[i] = ks * (z >= 0.f ? 1.f / d : e / d);   // a NaN z takes the second branch: NaN / NaN
-    acc += fmaxf(z, 0.f) + log1pf(e);              // fmaxf drops a NaN, log1pf(e) brings it back
+    return fmaxf(z, 0.f) + log1pf(e);              // fmaxf drops a NaN, log1pf(e) brings it back
   }
-  sh[t] = acc;
-  __syncthreads();
-  for (int h = ADV_THREADS / 2; h >= 1; h >>= 1) {
-    if (t < h) sh[t] += sh[t + h];
-    __syncthreads();
-  }
-  if (t == 0) partial[s] = sh[0];
-}
-
-__global__ void adv_bce_final_kernel(const float *__restrict__ partial, int S, float n, float *loss) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  float acc = partial[0];
-  for (int s = 1; s < S; ++s) acc += partial[s];
-  *loss = *loss + acc / n;
-}
+};
 
 }  // namespace dib
 
@@ -163,7 +133,7 @@ extern "C" int dib_leaky_relu_mask_backward_f16(const void *grad_dev, const unsi
 
 extern "C" size_t dib_adv_bce_loss_workspace_bytes(long long n) {
   if (n <= 0) return 0;
-  return (size_t)adv_slices(n) * sizeof(float);
+  return (size_t)scalar_slices(n) * sizeof(float);
 }
 
 extern "C" int dib_adv_bce_loss(const float *logits_dev, long long n, int real_label, float gscale, float *grad_dev, float *loss_dev,
@@ -174,12 +144,5 @@ extern "C" int dib_adv_bce_loss(const float *logits_dev, long long n, int real_l
   if (!logits_dev || !grad_dev || !loss_dev || !work_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
   const uintptr_t bits = (uintptr_t)logits_dev | (uintptr_t)grad_dev | (uintptr_t)loss_dev | (uintptr_t)work_dev;
   if ((bits & 3) != 0) { set_error("%s: tensors must be 4-byte aligned", who); return DIB_EINVAL; }
-  const int S = adv_slices(n);
-  const float denom = (float)n;
-  hipLaunchKernelGGL(adv_bce_partial_kernel, dim3((unsigned)S), dim3(ADV_THREADS), 0, (hipStream_t)stream, logits_dev, n, S, real_label,
-                     gscale / denom, grad_dev, (float *)work_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(adv_bce_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float *)work_dev, S, denom, loss_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return sliced_sum_run(BceTerm{logits_dev, real_label, gscale / (float)n, grad_dev}, n, loss_dev, (float *)work_dev, (hipStream_t)stream);
 }

@@ -1,5 +1,5 @@
 // The value half of DeepDeblur's patch augmentation (reference models/deblur/dataCommon.py: augment :72-87 with change_saturation,
-// add_noise :43-54), fused with the data movement of dib_deblur_patches (dib_deblur_train.hip, patches_kernel: crop, flips, transpose,
+// add_noise :43-54), fused with the data movement of dib_deblur_patches (the patch map of dib_deblur_patch.h: crop, flips, transpose,
 // channel order).  Both steps are pointwise per pixel, so they commute with that movement and ride in its launch: one lane per output
 // pixel loads its three channels through the composed index map, and stores three fp32 values.  As torch ops the same chain is about
 // twenty small kernels per list.  HBM-bound; no LDS, no scratch, no atomics, caller's stream (capturable).
@@ -17,24 +17,20 @@
 //                                                       follow see exactly g
 // models/deblur_train.py (augment_patches_torch) restates this op for op; tests/test_deblur_augment*.py hold both to a float64 HSV
 // round trip.
-#include "dib_common.h"
+#include "dib_deblur_patch.h"
 #include "dib_philox_dev.h"
 #include <hip/hip_fp16.h>
 #include <math.h>
 
 namespace dib {
 
-constexpr int AUG_MAX_BATCH = 64;      // as PATCH_MAX_BATCH: 64 descriptors of 48 bytes are 3 KB of the 4 KB of kernel arguments
 struct AugmentDesc {
-  const void *in;       // planar [3][H][W]
-  int H, W, py, px;
-  unsigned flags;       // dib_deblur_patches' word
+  PatchDesc p;
   float a, sigma;       // saturation factor; noise sigma in grey levels (0: none)
   unsigned key0, key1;  // Philox key of this image's noise field
-  int pad_;
 };
 static_assert(sizeof(AugmentDesc) == 48, "64 descriptors must stay under the kernel-argument limit");
-struct AugmentBatch { AugmentDesc d[AUG_MAX_BATCH]; };
+struct AugmentBatch { AugmentDesc d[PATCH_MAX_BATCH]; };
 
 template <typename T> __device__ __forceinline__ float quantised(T v);
 // (x * 255) in the image's own dtype, truncated towards zero, clamped to 0..255, NaN -> 0: dib_deblur.hip's quantise
@@ -49,7 +45,7 @@ template <> __device__ __forceinline__ float quantised<__half>(__half v) {
 
 __device__ __forceinline__ float clamp255(float v) { return fminf(fmaxf(v, 0.0f), 255.0f); }
 
-// grid (ceil(ps^2 / 256), B); the index map is patches_kernel's, read backwards from the output element
+// grid (ceil(ps^2 / 256), B)
 template <typename T>
 __global__ __launch_bounds__(256) void patches_augment_kernel(AugmentBatch batch, int ps, float *__restrict__ out) {
 #pragma clang fp contract(off)
@@ -58,15 +54,9 @@ __global__ __launch_bounds__(256) void patches_augment_kernel(AugmentBatch batch
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= n) return;
   const int y = (int)(e / (unsigned)ps), x = (int)(e % (unsigned)ps);
-  const bool rot = d.flags & DIB_PATCH_ROT90;
-  const int y2 = rot ? x : y, x2 = rot ? y : x;
-  const int y1 = (d.flags & DIB_PATCH_VFLIP) ? ps - 1 - y2 : y2;
-  const int x0 = (d.flags & DIB_PATCH_HFLIP) ? ps - 1 - x2 : x2;
-  const T *src = (const T *)d.in;
-  const size_t plane = (size_t)d.H * d.W, at = (size_t)(d.py + y1) * d.W + (d.px + x0);
   float q[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) q[c] = quantised<T>(src[(size_t)((d.flags >> (4 + 2 * c)) & 3u) * plane + at]);
+  for (int c = 0; c < 3; ++c) q[c] = quantised<T>(((const T *)d.p.in)[patch_source(d.p, ps, c, y, x)]);
   const float m = fmaxf(fmaxf(q[0], q[1]), q[2]);
   float *o = out + (size_t)blockIdx.y * 3 * n + e;
 #pragma unroll
@@ -90,29 +80,22 @@ extern "C" int dib_deblur_patches_augment(const void *const *in_dev, int dtype, 
                                           int B, int ps, float *out_dev, void *stream) {
   static const char who[] = "dib_deblur_patches_augment";
   if (dtype != DIB_F16 && dtype != DIB_F32) { set_error("%s: unknown dtype %d", who, dtype); return DIB_EINVAL; }
-  if (B < 0 || B > AUG_MAX_BATCH || ps < 1 || ps > 32768) { set_error("%s: needs 0 <= B <= %d and 1 <= ps <= 32768", who, AUG_MAX_BATCH); return DIB_EINVAL; }
+  if (B < 0 || B > PATCH_MAX_BATCH || ps < 1 || ps > 32768) { set_error("%s: needs 0 <= B <= %d and 1 <= ps <= 32768", who, PATCH_MAX_BATCH); return DIB_EINVAL; }
   if (B == 0) return DIB_OK;
   if (!in_dev || !H || !W || !py || !px || !flags || !saturation || !sigma || !keys || !out_dev) { set_error("%s: null pointer", who); return DIB_EINVAL; }
   if (((uintptr_t)out_dev & 3) != 0) { set_error("%s: out_dev must be 4-byte aligned", who); return DIB_EINVAL; }
   const size_t elem = dtype == DIB_F16 ? 2 : 4;
   AugmentBatch batch;
   for (int b = 0; b < B; ++b) {
-    if (!in_dev[b] || ((uintptr_t)in_dev[b] & (elem - 1)) != 0) { set_error("%s: image %d: null or misaligned pointer", who, b); return DIB_EINVAL; }
-    if (H[b] < ps || W[b] < ps || py[b] < 0 || px[b] < 0 || py[b] > H[b] - ps || px[b] > W[b] - ps) {
-      set_error("%s: image %d: a %d x %d patch at (%d, %d) leaves the %d x %d image", who, b, ps, ps, py[b], px[b], H[b], W[b]);
-      return DIB_ESHAPE;
-    }
-    const unsigned f = flags[b];
-    if ((f & ~(7u | (63u << 4))) != 0 || ((f >> 4) & 3u) == 3u || ((f >> 6) & 3u) == 3u || ((f >> 8) & 3u) == 3u) {
-      set_error("%s: image %d: flags 0x%x (three flip bits, three channel indices 0..2 in bits 4..9)", who, b, f);
-      return DIB_EINVAL;
-    }
+    AugmentDesc &d = batch.d[b];
+    const int code = patch_desc(who, b, in_dev[b], elem, H[b], W[b], py[b], px[b], flags[b], ps, &d.p);
+    if (code != DIB_OK) return code;
     if (!isfinite(saturation[b]) || saturation[b] < 0.0f) {
       set_error("%s: image %d: saturation %g (needs a finite factor of at least 0)", who, b, (double)saturation[b]);
       return DIB_EINVAL;
     }
     if (!isfinite(sigma[b])) { set_error("%s: image %d: sigma %g (needs a finite noise level)", who, b, (double)sigma[b]); return DIB_EINVAL; }
-    batch.d[b] = {in_dev[b], H[b], W[b], py[b], px[b], f, saturation[b], sigma[b], keys[2 * b], keys[2 * b + 1], 0};
+    d.a = saturation[b], d.sigma = sigma[b], d.key0 = keys[2 * b], d.key1 = keys[2 * b + 1];
   }
   const dim3 grid((unsigned)(((long long)ps * ps + 255) / 256), (unsigned)B);
   if (dtype == DIB_F16) hipLaunchKernelGGL(patches_augment_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, batch, ps, out_dev);

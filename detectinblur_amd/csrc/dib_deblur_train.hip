@@ -10,60 +10,32 @@
 //                            backward of the convolution epilogue: grad_out = mask bit ? grad_in : 0 (relu_mask_bwd_kernel's
 //                            select, bit for bit) and bias_grad[c] = sum over pixels of grad_out[p][c] from the same pass: the
 //                            gradient is read once, where the mask pass followed by torch's channel sum reads it twice.
-//   (c) l1_partial_kernel + l1_final_kernel
+//   (c) sliced_sum_partial_kernel<L1Term> + sliced_sum_final_kernel
 //                            one level of the multi-scale L1 loss: sum |out - target| / (3 n_pix) added into a device scalar, and
 //                            the gradient sign(out - target) * k stored beside it.
 //
-// THE SUMMATION ORDER of (b) and (c) is fixed by the shape alone, so two calls on the same input agree bit for bit:
-//   (b) the [n_pix][C] gradient is cut into S slices of consecutive pixels (bias_grad_geometry below: S = ceil(n_pix / (16 R))
-//       capped at 1024).  A workgroup of 256 lanes takes one slice and QB = min(C / V, 256) lane columns (V = 4 channels per lane
-//       when C % 4 == 0, else 1; the Half form, dib_bias_grad_f16_nhwc: V = 8 when C % 8 == 0 and the gradient is 16-byte aligned,
-//       else 1 -- one 16-byte load per lane either way, and every Half is exact in fp32, so only the additions below round); lane
-//       (row, column) adds the pixels slice_begin + row, + R, + 2 R, ... (R = 256 / QB) one after the other: a chain of at most L = ceil(slice length / R) additions.  The R rows are then added in LDS as a tree (row r takes row
-//       r + h for h = the powers of two below R, largest first): ceil(log2 R) levels.  The slice's partial sums go to the workspace
-//       [S][C]; the second launch adds them for each channel in slice order, starting from slice 0: S - 1 additions.
-//       DEPTH of the tree, the number of fp32 additions any one input can pass through:  L + ceil(log2 R) + S - 1.
-//       Every addition rounds once, so |bias_grad - exact| <= depth * 2^-24 * sum |grad_out| (first order in 2^-24).
-//   (c) the 3 n_pix differences, in memory order, are cut into S = ceil(3 n_pix / 2048) (capped at 1024) slices; lane t of a
-//       slice's workgroup adds |d| of elements slice_begin + t, + 256, ...: a chain of L = ceil(slice length / 256); the 256 lanes
-//       are added as a tree of 8 levels; the second launch adds the S partial sums in slice order, divides by float(3 n_pix) and adds
-//       the result to the loss scalar.  DEPTH = L + 8 + S - 1 additions, then one division and one addition onto the scalar.
-// models/deblur_train.py restates both geometries (bias_grad_depth, l1_loss_depth) for the tests' error bounds.  The order itself is
-// restated in numpy float32 from this comment (tests/test_deblur_train.py: restated_bias_grad, restated_l1), and
-// tests/test_deblur_train_geometry_gpu.py holds the kernels to it bit for bit at S = 1024: change the order here and there together.
+// The patch map of (a): dib_deblur_patch.h.  THE SUMMATION ORDER of (b) and (c), fixed by the shape alone, and the depth of its tree:
+// dib_sliced_sum.h; what is here of it is (b)'s two-dimensional geometry (bias_grad_geometry) and the terms of (c).
+#include "dib_deblur_patch.h"
 #include "dib_eltwise_vec.h"      // host side: misaligned, launch; F32Lane::select, F16Lane::select
+#include "dib_sliced_sum.h"
 
 namespace dib {
 
 // ---- (a) patches -----------------------------------------------------------------------------------------------------------------
-constexpr int PATCH_MAX_BATCH = 64;
-struct PatchDesc {
-  const void *in;      // planar [3][H][W]
-  int H, W, py, px;
-  unsigned flags;      // DIB_PATCH_HFLIP | DIB_PATCH_VFLIP | DIB_PATCH_ROT90 | channel order in bits 4..9
-  int pad_;
-};
 struct PatchBatch { PatchDesc d[PATCH_MAX_BATCH]; };
 
-// out[b][c][y][x] = in_b[order[c]][py + y1][px + x0]: dataCommon.py's order -- crop, hflip (reverse x), vflip (reverse y), rot90
-// (transpose), channel order -- read backwards from the output element.
 template <typename T>
 __global__ __launch_bounds__(256) void patches_kernel(PatchBatch batch, int ps, T *__restrict__ out) {
   const PatchDesc d = batch.d[blockIdx.z];
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (unsigned)(ps * ps)) return;
   const int c = blockIdx.y, y = (int)(e / (unsigned)ps), x = (int)(e % (unsigned)ps);
-  const bool rot = d.flags & DIB_PATCH_ROT90;
-  const int y2 = rot ? x : y, x2 = rot ? y : x;
-  const int y1 = (d.flags & DIB_PATCH_VFLIP) ? ps - 1 - y2 : y2;
-  const int x0 = (d.flags & DIB_PATCH_HFLIP) ? ps - 1 - x2 : x2;
-  const int cs = (int)((d.flags >> (4 + 2 * c)) & 3u);
-  const T *src = (const T *)d.in;
-  out[((size_t)blockIdx.z * 3 + c) * ps * ps + e] = src[((size_t)cs * d.H + (d.py + y1)) * d.W + (d.px + x0)];
+  out[((size_t)blockIdx.z * 3 + c) * ps * ps + e] = ((const T *)d.in)[patch_source(d, ps, c, y, x)];
 }
 
 // ---- (b) bias gradient -----------------------------------------------------------------------------------------------------------
-constexpr int BG_THREADS = 256, BG_MAX_SLICES = 1024, BG_PIXELS_PER_LANE = 16;
+constexpr int BG_THREADS = SS_THREADS, BG_PIXELS_PER_LANE = 16;
 
 struct BiasGradGeom {
   long long npix;
@@ -71,8 +43,6 @@ struct BiasGradGeom {
   int CV, QB, R;   // lane columns in all, per workgroup, pixel rows per workgroup
   int chunks, S;   // workgroups side by side, pixel slices
 };
-
-__host__ __device__ inline long long bg_slice_begin(long long n, int S, int s) { return n / S * s + (n % S < s ? n % S : s); }
 
 static BiasGradGeom bias_grad_geometry(long long npix, int C, int V) {
   BiasGradGeom g;
@@ -83,11 +53,7 @@ static BiasGradGeom bias_grad_geometry(long long npix, int C, int V) {
   g.QB = g.CV < BG_THREADS ? g.CV : BG_THREADS;
   g.R = BG_THREADS / g.QB;
   g.chunks = (g.CV + g.QB - 1) / g.QB;
-  const long long per = (long long)g.R * BG_PIXELS_PER_LANE;
-  long long S = (npix + per - 1) / per;
-  if (S > BG_MAX_SLICES) S = BG_MAX_SLICES;
-  if (S < 1) S = 1;
-  g.S = (int)S;
+  g.S = slice_count(npix, (long long)g.R * BG_PIXELS_PER_LANE);
   return g;
 }
 
@@ -151,8 +117,8 @@ __global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typ
   const bool active = row < g.R && q < g.CV;
   T acc = BgVec<V>::zero();
   if (active) {
-    const long long p1 = bg_slice_begin(g.npix, g.S, s + 1);
-    for (long long p = bg_slice_begin(g.npix, g.S, s) + row; p < p1; p += g.R) {
+    const long long p1 = slice_begin(g.npix, g.S, s + 1);
+    for (long long p = slice_begin(g.npix, g.S, s) + row; p < p1; p += g.R) {
       const long long i = p * g.CV + q;
       typename St::Raw v = grad_in[i];
       if (MASK) v = St::select(v, mask[i]);
@@ -162,12 +128,7 @@ __global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typ
   }
   sh[t] = acc;
   __syncthreads();
-  int h = 1;
-  while (h < g.R) h <<= 1;
-  for (h >>= 1; h >= 1; h >>= 1) {
-    if (active && row < h && row + h < g.R) sh[t] = BgVec<V>::add(sh[t], sh[t + h * g.QB]);
-    __syncthreads();
-  }
+  row_tree<BgVec<V>>(sh, t, row, active, g.R, g.QB);
   if (active && row == 0) BgVec<V>::store(partial + (long long)s * g.C + (long long)q * V, sh[t]);
 }
 
@@ -177,7 +138,7 @@ __global__ __launch_bounds__(BG_THREADS) void bias_grad_partial_kernel(const typ
 // row from LDS, slice 0 first.  Rows are padded by one word so that the four adding lanes read four different banks.
 constexpr int BG_FINAL_CH = 4;
 __global__ __launch_bounds__(BG_THREADS) void bias_grad_final_kernel(const float *__restrict__ partial, int S, int C, float *__restrict__ bias_grad) {
-  __shared__ float sh[BG_FINAL_CH][BG_MAX_SLICES + 1];
+  __shared__ float sh[BG_FINAL_CH][SS_MAX_SLICES + 1];
   const int c0 = blockIdx.x * BG_FINAL_CH, t = threadIdx.x;
   for (int s = t; s < S; s += BG_THREADS)
 #pragma unroll
@@ -207,45 +168,20 @@ static int bias_grad_run(const void *grad_in, const unsigned char *mask, void *g
 }
 
 // ---- (c) L1 loss of one pyramid level -----------------------------------------------------------------------------------------
-constexpr int L1_THREADS = 256, L1_MAX_SLICES = 1024, L1_ELEMS_PER_LANE = 8;
-
-static int l1_slices(long long n_elems) {
-  const long long per = (long long)L1_THREADS * L1_ELEMS_PER_LANE;
-  long long S = (n_elems + per - 1) / per;
-  if (S > L1_MAX_SLICES) S = L1_MAX_SLICES;
-  return S < 1 ? 1 : (int)S;
-}
-
-// d = out - target; grad = sign(d) * k: +-k, 0 for d == 0 (either sign of zero), d itself (a NaN) when d is a NaN
-__global__ __launch_bounds__(L1_THREADS) void l1_partial_kernel(const float *__restrict__ out, const float *__restrict__ target, int t_stride,
-                                                                long long n_elems, int S, float k, float *__restrict__ grad,
-                                                                float *__restrict__ partial) {
-  __shared__ float sh[L1_THREADS];
-  const int t = threadIdx.x, s = blockIdx.x;
-  const long long e1 = bg_slice_begin(n_elems, S, s + 1);
-  float acc = 0.f;
-  for (long long e = bg_slice_begin(n_elems, S, s) + t; e < e1; e += L1_THREADS) {
+struct L1Term {
+  const float *out, *target;
+  int t_stride;
+  float k;
+  float *grad;
+  // d = out - target; grad = sign(d) * k: +-k, 0 for d == 0 (either sign of zero), d itself (a NaN) when d is a NaN
+  __device__ __forceinline__ float operator()(long long e) const {
     const long long p = e / 3;
     const int c = (int)(e - p * 3);
     const float d = out[e] - target[p * t_stride + c];
     grad[e] = d != d ? d : d > 0.f ? k : d < 0.f ? -k : 0.f;
-    acc += fabsf(d);
+    return fabsf(d);
   }
-  sh[t] = acc;
-  __syncthreads();
-  for (int h = L1_THREADS / 2; h >= 1; h >>= 1) {
-    if (t < h) sh[t] += sh[t + h];
-    __syncthreads();
-  }
-  if (t == 0) partial[s] = sh[0];
-}
-
-__global__ void l1_final_kernel(const float *__restrict__ partial, int S, float n, float *loss) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  float acc = partial[0];
-  for (int s = 1; s < S; ++s) acc += partial[s];
-  *loss = *loss + acc / n;
-}
+};
 
 }  // namespace dib
 
@@ -262,17 +198,8 @@ extern "C" int dib_deblur_patches(const void *const *in_dev, int dtype, const in
   if (((uintptr_t)out_dev & (elem - 1)) != 0) { set_error("%s: out_dev must be aligned to its element", who); return DIB_EINVAL; }
   PatchBatch batch;
   for (int b = 0; b < B; ++b) {
-    if (!in_dev[b] || ((uintptr_t)in_dev[b] & (elem - 1)) != 0) { set_error("%s: image %d: null or misaligned pointer", who, b); return DIB_EINVAL; }
-    if (H[b] < ps || W[b] < ps || py[b] < 0 || px[b] < 0 || py[b] > H[b] - ps || px[b] > W[b] - ps) {
-      set_error("%s: image %d: a %d x %d patch at (%d, %d) leaves the %d x %d image", who, b, ps, ps, py[b], px[b], H[b], W[b]);
-      return DIB_ESHAPE;
-    }
-    const unsigned f = flags[b];
-    if ((f & ~(7u | (63u << 4))) != 0 || ((f >> 4) & 3u) == 3u || ((f >> 6) & 3u) == 3u || ((f >> 8) & 3u) == 3u) {
-      set_error("%s: image %d: flags 0x%x (three flip bits, three channel indices 0..2 in bits 4..9)", who, b, f);
-      return DIB_EINVAL;
-    }
-    batch.d[b] = {in_dev[b], H[b], W[b], py[b], px[b], f, 0};
+    const int code = patch_desc(who, b, in_dev[b], elem, H[b], W[b], py[b], px[b], flags[b], ps, &batch.d[b]);
+    if (code != DIB_OK) return code;
   }
   const dim3 grid((unsigned)(((long long)ps * ps + 255) / 256), 3u, (unsigned)B);
   if (dtype == DIB_F16) hipLaunchKernelGGL(patches_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, batch, ps, (unsigned short *)out_dev);
@@ -334,7 +261,7 @@ extern "C" int dib_bias_grad_f16_nhwc(const void *grad_in_dev, const unsigned ch
 
 extern "C" size_t dib_l1_pyramid_loss_workspace_bytes(long long n_pix) {
   if (n_pix <= 0) return 0;
-  return (size_t)l1_slices(3 * n_pix) * sizeof(float);
+  return (size_t)scalar_slices(3 * n_pix) * sizeof(float);
 }
 
 extern "C" int dib_l1_pyramid_loss(const float *out_dev, const float *target_dev, int target_stride, long long n_pix, float gscale,
@@ -346,12 +273,5 @@ extern "C" int dib_l1_pyramid_loss(const float *out_dev, const float *target_dev
   const uintptr_t bits = (uintptr_t)out_dev | (uintptr_t)target_dev | (uintptr_t)grad_dev | (uintptr_t)loss_dev | (uintptr_t)work_dev;
   if ((bits & 3) != 0) { set_error("%s: tensors must be 4-byte aligned", who); return DIB_EINVAL; }
   const long long n = 3 * n_pix;
-  const int S = l1_slices(n);
-  const float denom = (float)n;
-  hipLaunchKernelGGL(l1_partial_kernel, dim3((unsigned)S), dim3(L1_THREADS), 0, (hipStream_t)stream, out_dev, target_dev, target_stride, n, S,
-                     gscale / denom, grad_dev, (float *)work_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float *)work_dev, S, denom, loss_dev);
-  DIB_HIP_CHECK(hipGetLastError());
-  return DIB_OK;
+  return sliced_sum_run(L1Term{out_dev, target_dev, target_stride, gscale / (float)n, grad_dev}, n, loss_dev, (float *)work_dev, (hipStream_t)stream);
 }

@@ -18,15 +18,15 @@ itself, is not in the reference tree: binary cross-entropy with logits against t
               * "torch" / "torch-amp": the plain module (under torch.autocast(dtype=float16) for Half input): everything else.
   loss      `adv_bce(logits, real_label)` / `adv_bce_sum([(logits, label), ...])`: mean binary cross-entropy with logits against a
             constant label, all terms added into ONE device scalar by one autograd node (dib_adv_bce_loss per term stores that term's
-            gradient; the backward scales it by the incoming gradient) -- `_L1Pyramid`'s shape.  fp32 logits; the --amp step hands it
+            gradient; the backward scales it by the incoming gradient) -- `pyramid_l1_loss`'s node.  fp32 logits; the --amp step hands it
             `logits.float()`.  There is no Half loss kernel.  Elsewhere (CPU, tests) `adv_bce_torch`, the same formulas in torch ops.
 
-Summation order of the loss and the depth of its tree: csrc/dib_deblur_adv.hip; restated below as `adv_loss_depth`."""
+Summation order of the loss and the depth of its tree: csrc/dib_sliced_sum.h; `adv_loss_depth`."""
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .deblur_train import _ceil_div, sign_mask_torch
+from .deblur_train import choose_path, lanes, mask_bits_torch, nhwc_grad, sign_mask_torch, sliced_sum_depth, stored_grad_sum
 
 # False: the plain module on the GPU too, for A/B runs (the tests switch it on themselves).  On: 306.04 against 308.49 ms per step at the
 # trainer's defaults with --loss 1*L1+1*ADV on an MI355X, 103.64 against 105.47 under --amp; four rounds, the order reversed in every
@@ -97,10 +97,6 @@ class Discriminator(nn.Module):
 
 # ---- LeakyReLU with a sign mask ------------------------------------------------------------------------------------------------------
 
-def _lane(dtype):
-    return 8 if dtype == torch.float16 else 4
-
-
 def leaky_mask_torch(x, slope=SLOPE):
     """dib_leaky_relu_mask[_f16] restated: -> (x > 0 ? x : x * slope with Half multiplied in fp32 and rounded once, the sign mask of the
     result: `sign_mask_torch`, one byte per 4 fp32 / 8 Half elements).  Bit-equal to F.leaky_relu on the CPU; on gfx950 torch's Half
@@ -111,16 +107,14 @@ def leaky_mask_torch(x, slope=SLOPE):
 
 def leaky_grad_torch(grad, mask, slope=SLOPE):
     """dib_leaky_relu_mask_backward[_f16] restated: bit ? grad : grad * slope.  Bit-equal to F.leaky_relu's autograd backward."""
-    n = _lane(grad.dtype)
-    bits = ((mask.reshape(-1, 1) >> torch.arange(n, device=mask.device, dtype=torch.uint8)) & 1).reshape(grad.shape).bool()
-    return torch.where(bits, grad, (grad.float() * slope).to(grad.dtype))
+    return torch.where(mask_bits_torch(mask, grad), grad, (grad.float() * slope).to(grad.dtype))
 
 
 def leaky_mask_device(x, slope=SLOPE, want_mask=True):
     """dib_leaky_relu_mask[_f16] in place on a dense fp32 or Half CUDA tensor -> the mask (None when not asked for)."""
     from .. import _lib
     l = _lib.lib()
-    mask = torch.empty(x.numel() // _lane(x.dtype), dtype=torch.uint8, device=x.device) if want_mask else None
+    mask = torch.empty(x.numel() // lanes(x.dtype), dtype=torch.uint8, device=x.device) if want_mask else None
     run = l.dib_leaky_relu_mask_f16 if x.dtype == torch.float16 else l.dib_leaky_relu_mask
     _lib.check(run(x.data_ptr(), x.numel(), slope, mask.data_ptr() if want_mask else None, _lib.stream_of(x)))
     return mask
@@ -153,12 +147,7 @@ class _LeakyMask(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        if not grad.is_contiguous(memory_format=torch.channels_last):
-            grad = grad.contiguous(memory_format=torch.channels_last)      # the mask is in NHWC element order
-        if grad.data_ptr() & 15:
-            grad = grad.clone(memory_format=torch.channels_last)
-        # not in place: autograd may hand the same gradient tensor to another node
-        return leaky_grad_device(grad, ctx.saved_tensors[0], ctx.slope), None
+        return leaky_grad_device(nhwc_grad(grad), ctx.saved_tensors[0], ctx.slope), None
 
 
 # ---- the network's two paths ---------------------------------------------------------------------------------------------------------
@@ -170,7 +159,7 @@ def _amp(D, x):
 
 def _hip_ok(D, x):
     p = next(D.parameters())
-    lane = _lane(x.dtype)
+    lane = lanes(x.dtype)
     return (FUSE_DEBLUR_ADV and p.is_cuda and p.dtype == torch.float32 and x.is_cuda and x.device == p.device
             and x.dtype in (torch.float32, torch.float16) and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0
             and all(b * c * h * w > 0 and b * c * h * w % lane == 0 for b, c, h, w in D.activation_shapes(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]))))
@@ -192,27 +181,14 @@ def discriminator_forward(D, x):
     """x: [B, 3, H, W] on the 0..255 scale, fp32 or Half (Half into fp32 parameters: the --amp form) -> the logits [B, 1, h, w], one
     per image when the smaller side is 193..., in x's dtype.  `D.last_path`: "hip" / "hip-amp" / "torch" / "torch-amp"."""
     D.check_size(x)
-    if _amp(D, x):
-        if _hip_ok(D, x):
-            out, D.last_path = _forward_hip(D, x), "hip-amp"
-        else:
-            with torch.autocast(x.device.type, dtype=torch.float16):
-                out = D(x)
-            D.last_path = "torch-amp"
-    elif _hip_ok(D, x):
-        out, D.last_path = _forward_hip(D, x), "hip"
-    else:
-        out, D.last_path = D(x), "torch"
-    return out
+    return choose_path(D, _amp(D, x), _hip_ok(D, x), lambda: _forward_hip(D, x), lambda: D(x))
 
 
 # ---- the loss ------------------------------------------------------------------------------------------------------------------------
 
 def adv_loss_depth(n):
-    """Additions any one term of dib_adv_bce_loss's sum can pass through (csrc/dib_deblur_adv.hip, "THE SUMMATION ORDER"): the order of
-    dib_l1_pyramid_loss over n elements; the division and the addition onto the scalar come on top."""
-    S = max(1, min(1024, _ceil_div(n, 2048)))
-    return _ceil_div(_ceil_div(n, S), 256) + 8 + S - 1
+    """Additions any one term of dib_adv_bce_loss's sum over n logits can pass through."""
+    return sliced_sum_depth(n)
 
 
 def adv_bce_terms_torch(logits, real_label, gscale=1.0):
@@ -228,25 +204,19 @@ def adv_bce_terms_torch(logits, real_label, gscale=1.0):
     return grad, term.sum() / n.to(logits.device)
 
 
-class _AdvBCETorch(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, labels, *logits):
-        grads, loss = [], 0.0
-        for x, label in zip(logits, labels):
-            g, term = adv_bce_terms_torch(x, label)
-            grads.append(g)
-            loss = loss + term
-        ctx.save_for_backward(*grads)
-        return loss
+def _bce_term_torch(x, label, loss):
+    grad, term = adv_bce_terms_torch(x, label)
+    loss += term
+    return grad
 
-    @staticmethod
-    def backward(ctx, grad):
-        return (None,) + tuple(g * grad for g in ctx.saved_tensors)
+
+def _bce_term_device(x, label, loss):
+    return adv_bce_device(x.contiguous(), label, loss).view_as(x)
 
 
 def adv_bce_torch(logits, real_label):
     """`adv_bce` in torch ops, with the kernel's gradient formula (sigma(0) = 1 / 2, which autograd through max() would not give)."""
-    return _AdvBCETorch.apply([int(real_label)], logits)
+    return stored_grad_sum(_bce_term_torch, [logits], [int(real_label)])
 
 
 def adv_bce_device(logits, real_label, loss, gscale=1.0):
@@ -261,21 +231,6 @@ def adv_bce_device(logits, real_label, loss, gscale=1.0):
     return grad
 
 
-class _AdvBCE(torch.autograd.Function):
-    """sum over (logits, label) pairs of the mean BCE as one node: dib_adv_bce_loss per pair adds into one device scalar and stores that
-    pair's gradient; the backward scales the stored gradients by the incoming one."""
-
-    @staticmethod
-    def forward(ctx, labels, *logits):
-        loss = torch.zeros(1, dtype=torch.float32, device=logits[0].device)
-        ctx.save_for_backward(*[adv_bce_device(x.contiguous(), label, loss).view_as(x) for x, label in zip(logits, labels)])
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, grad):
-        return (None,) + tuple(g * grad for g in ctx.saved_tensors)
-
-
 def _bce_hip_ok(logits):
     return FUSE_DEBLUR_ADV and all(x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 for x in logits)
 
@@ -285,7 +240,7 @@ def adv_bce_sum(pairs):
     logits, labels = [p[0] for p in pairs], [int(p[1]) for p in pairs]
     if any(l not in (0, 1) for l in labels):
         raise ValueError("adv_bce: labels are 0 (fake) or 1 (real)")
-    return (_AdvBCE if _bce_hip_ok(logits) else _AdvBCETorch).apply(labels, *logits)
+    return stored_grad_sum(_bce_term_device if _bce_hip_ok(logits) else _bce_term_torch, logits, labels)
 
 
 def adv_bce(logits, real_label):

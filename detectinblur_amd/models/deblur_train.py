@@ -49,8 +49,9 @@ model.py); `python -m detectinblur_amd.train_deblurrer` is this project's, fed b
             gradient of a level loses bits, or all of them, without an inf to skip the step on: 3.3e-4 at the defaults (level 0:
             n_pix = 16 x 256 x 256) with scale 1024; GradScaler halves the scale on an overflow and never looks below.
 
-Summation orders and the depth of their trees (for error bounds): csrc/dib_deblur_train.hip; restated below as `bias_grad_depth`
-and `l1_loss_depth`."""
+Summation order and the depth of its tree (for error bounds): csrc/dib_sliced_sum.h; restated below as `bias_grad_depth` and
+`sliced_sum_depth`.  models/deblur_adversarial.py takes from here what its discriminator and loss share with the generator's: `lanes`,
+`mask_bits_torch`, `nhwc_grad`, `sliced_sum_depth`, `choose_path` and `stored_grad_sum`."""
 import collections
 import ctypes
 import math
@@ -124,22 +125,28 @@ def gather_patches_torch(images, draws, ps):
     return torch.stack(out).contiguous()
 
 
-def gather_patches_device(images, draws, ps):
+def _patch_chunks(who, images, draws):
+    """What both patch entry points take per image: checks the images, then for each run of at most PATCH_MAX_BATCH of them yields
+    (first index, draws, the leading arguments of the call: pointers, dtype, H, W, py, px, flags)."""
     from .. import _lib
     first = images[0]
     if first.dtype not in (torch.float16, torch.float32) or any(im.dtype != first.dtype or im.device != first.device or im.dim() != 3
                                                                   or im.shape[0] != 3 for im in images):
-        raise ValueError("gather_patches: planar [3, H, W] Half or fp32 images of one dtype on one device")
+        raise ValueError("%s: planar [3, H, W] Half or fp32 images of one dtype on one device" % who)
     images = [im.contiguous() for im in images]
-    out = torch.empty((len(images), 3, ps, ps), dtype=first.dtype, device=first.device)
     dtype = _lib.DIB_F16 if first.dtype == torch.float16 else _lib.DIB_F32
     for b0 in range(0, len(images), PATCH_MAX_BATCH):
         ims, ds = images[b0:b0 + PATCH_MAX_BATCH], draws[b0:b0 + PATCH_MAX_BATCH]
-        flags = (ctypes.c_uint * len(ims))(*[flags_word(d) for d in ds])
-        _lib.check(_lib.lib().dib_deblur_patches(_lib.ptr_array([im.data_ptr() for im in ims]), dtype,
-                                                 _lib.int_array([int(im.shape[1]) for im in ims]), _lib.int_array([int(im.shape[2]) for im in ims]),
-                                                 _lib.int_array([d.py for d in ds]), _lib.int_array([d.px for d in ds]), flags, len(ims), ps,
-                                                 out[b0].data_ptr(), _lib.stream_of(first)))
+        yield b0, ds, (_lib.ptr_array([im.data_ptr() for im in ims]), dtype, _lib.int_array([int(im.shape[1]) for im in ims]),
+                       _lib.int_array([int(im.shape[2]) for im in ims]), _lib.int_array([d.py for d in ds]),
+                       _lib.int_array([d.px for d in ds]), (ctypes.c_uint * len(ds))(*[flags_word(d) for d in ds]))
+
+
+def gather_patches_device(images, draws, ps):
+    from .. import _lib
+    out = torch.empty((len(images), 3, ps, ps), dtype=images[0].dtype, device=images[0].device)
+    for b0, ds, args in _patch_chunks("gather_patches", images, draws):
+        _lib.check(_lib.lib().dib_deblur_patches(*args, len(ds), ps, out[b0].data_ptr(), _lib.stream_of(out)))
     return out
 
 
@@ -183,26 +190,13 @@ def augment_patches_torch(images, draws, ps, noise, pre_rounding=False):
 
 def augment_patches_device(images, draws, ps, noise):
     from .. import _lib
-    first = images[0]
-    if first.dtype not in (torch.float16, torch.float32) or any(im.dtype != first.dtype or im.device != first.device or im.dim() != 3
-                                                                  or im.shape[0] != 3 for im in images):
-        raise ValueError("augment_patches: planar [3, H, W] Half or fp32 images of one dtype on one device")
-    images = [im.contiguous() for im in images]
-    out = torch.empty((len(images), 3, ps, ps), dtype=torch.float32, device=first.device)
-    dtype = _lib.DIB_F16 if first.dtype == torch.float16 else _lib.DIB_F32
-    for b0 in range(0, len(images), PATCH_MAX_BATCH):
-        # every per-image array is cut with the images
-        ims, ds = images[b0:b0 + PATCH_MAX_BATCH], draws[b0:b0 + PATCH_MAX_BATCH]
-        n = len(ims)
-        flags = (ctypes.c_uint * n)(*[flags_word(d) for d in ds])
+    out = torch.empty((len(images), 3, ps, ps), dtype=torch.float32, device=images[0].device)
+    for b0, ds, args in _patch_chunks("augment_patches", images, draws):
+        n = len(ds)
         saturation = (ctypes.c_float * n)(*[d.saturation for d in ds])
         sigma = (ctypes.c_float * n)(*[d.sigma if noise else 0.0 for d in ds])
         keys = (ctypes.c_uint * (2 * n))(*[int(k) & 0xFFFFFFFF for d in ds for k in d.key])
-        _lib.check(_lib.lib().dib_deblur_patches_augment(_lib.ptr_array([im.data_ptr() for im in ims]), dtype,
-                                                         _lib.int_array([int(im.shape[1]) for im in ims]),
-                                                         _lib.int_array([int(im.shape[2]) for im in ims]),
-                                                         _lib.int_array([d.py for d in ds]), _lib.int_array([d.px for d in ds]), flags,
-                                                         saturation, sigma, keys, n, ps, out[b0].data_ptr(), _lib.stream_of(first)))
+        _lib.check(_lib.lib().dib_deblur_patches_augment(*args, saturation, sigma, keys, n, ps, out[b0].data_ptr(), _lib.stream_of(out)))
     return out
 
 
@@ -267,7 +261,7 @@ def _ceil_div(a, b):
 
 
 def bias_grad_depth(n_pix, C, V=None):
-    """Additions any one input of dib_bias_grad_nhwc's channel sum can pass through (csrc/dib_deblur_train.hip, "THE SUMMATION ORDER").
+    """Additions any one input of dib_bias_grad_nhwc's channel sum can pass through (csrc/dib_sliced_sum.h, "THE SUMMATION ORDER").
     V: channels per lane; None is the fp32 form's (4 when C % 4 == 0, else 1).  dib_bias_grad_f16_nhwc on 16-byte aligned gradients:
     `bias_grad_lanes(C, torch.float16)`, 8 when C % 8 == 0, else 1."""
     if V is None:
@@ -281,37 +275,49 @@ def bias_grad_depth(n_pix, C, V=None):
     return L + (R - 1).bit_length() + S - 1
 
 
-def l1_loss_depth(n_pix):
-    """The same for dib_l1_pyramid_loss's sum of |d|; the division and the addition onto the scalar come on top."""
-    n = 3 * n_pix
+def sliced_sum_depth(n):
+    """The same for a scalar loss over n elements (csrc/dib_sliced_sum.h, "scalar losses"); the division and the addition onto the
+    scalar come on top."""
     S = max(1, min(1024, _ceil_div(n, 2048)))
     return _ceil_div(_ceil_div(n, S), 256) + 8 + S - 1
 
 
+def l1_loss_depth(n_pix):
+    """dib_l1_pyramid_loss's sum of |d|"""
+    return sliced_sum_depth(3 * n_pix)
+
+
+def lanes(dtype):
+    """Elements of a 16-byte lane, and with that per mask byte: 8 Half, 4 fp32."""
+    return 8 if dtype == torch.float16 else 4
+
+
 def bias_grad_lanes(C, dtype):
-    """Channels per lane of the bias-gradient kernels on 16-byte aligned gradients; also the elements per mask byte of that dtype."""
-    n = 8 if dtype == torch.float16 else 4
-    return n if C % n == 0 else 1
+    """Channels per lane of the bias-gradient kernels on 16-byte aligned gradients."""
+    return lanes(dtype) if C % lanes(dtype) == 0 else 1
 
 
 def sign_mask_torch(y):
     """dib_bias_act_mask_nhwc's mask of a [n_pix, C] (C % 4 == 0) tensor: one byte per 4 consecutive elements, bit k = element > 0.
     A Half `y` (C % 8 == 0): dib_bias_act_mask_f16_nhwc's, one byte per 8."""
-    n = 8 if y.dtype == torch.float16 else 4
-    bits = (y.reshape(-1, n) > 0).to(torch.uint8)
+    bits = (y.reshape(-1, lanes(y.dtype)) > 0).to(torch.uint8)
     mask = bits[:, 0]
-    for k in range(1, n):
+    for k in range(1, bits.shape[1]):
         mask = mask | (bits[:, k] << k)
     return mask
+
+
+def mask_bits_torch(mask, like):
+    """The bytes of `sign_mask_torch` back as one bool per element of `like`."""
+    shifts = torch.arange(lanes(like.dtype), device=mask.device, dtype=torch.uint8)
+    return ((mask.reshape(-1, 1) >> shifts) & 1).reshape(like.shape).bool()
 
 
 def bias_grad_torch(grad, mask=None):
     """dib_bias_grad_nhwc restated: grad [n_pix, C] -> (grad_out, bias_grad).  A Half `grad`: dib_bias_grad_f16_nhwc, with its mask
     of one byte per 8 elements, a Half grad_out and the fp32 sum of the upcast values."""
     if mask is not None:
-        n = 8 if grad.dtype == torch.float16 else 4
-        bits = ((mask.reshape(-1, 1) >> torch.arange(n, device=mask.device, dtype=torch.uint8)) & 1).reshape(grad.shape).bool()
-        grad = torch.where(bits, grad, torch.zeros((), dtype=grad.dtype, device=grad.device))
+        grad = torch.where(mask_bits_torch(mask, grad), grad, torch.zeros((), dtype=grad.dtype, device=grad.device))
     return grad, (grad.float() if grad.dtype == torch.float16 else grad).sum(0)
 
 
@@ -360,6 +366,16 @@ def _bias_act_forward(ctx, x, bias, residual, relu, act, act_mask, lane):
     return x
 
 
+def nhwc_grad(grad):
+    """An incoming gradient as the one-launch backwards take it: in NHWC element order (the mask's and the channel index's) and on 16
+    bytes.  They never write it in place: autograd may hand the same gradient tensor to another node."""
+    if not grad.is_contiguous(memory_format=torch.channels_last):
+        grad = grad.contiguous(memory_format=torch.channels_last)
+    if grad.data_ptr() & 15:
+        grad = grad.clone(memory_format=torch.channels_last)
+    return grad
+
+
 class _BiasActTrain(torch.autograd.Function):
     """x = act(x + bias[c] (+ residual)) in place on a channels-last fp32 CUDA convolution output (dib_bias_act_nhwc, or
     dib_bias_act_mask_nhwc with the ReLU); the backward is one launch pair over the gradient (dib_bias_grad_nhwc): masked gradient and
@@ -371,12 +387,7 @@ class _BiasActTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        if not grad.is_contiguous(memory_format=torch.channels_last):
-            grad = grad.contiguous(memory_format=torch.channels_last)      # the mask and the channel index are in NHWC element order
-        if grad.data_ptr() & 15:
-            grad = grad.clone(memory_format=torch.channels_last)
-        # not in place: autograd may hand the same gradient tensor to another node
-        grad, gb = bias_grad_device(grad, ctx.saved_tensors[0] if ctx.masked else None)
+        grad, gb = bias_grad_device(nhwc_grad(grad), ctx.saved_tensors[0] if ctx.masked else None)
         return grad, gb, (grad if ctx.has_res else None), None
 
 
@@ -401,7 +412,7 @@ def _hip_ok(model, levels, dtype=torch.float32):
     """`dtype`: of the levels (the parameters are fp32 either way); Half lanes hold 8 channels."""
     p = next(model.parameters())
     return (FUSE_DEBLUR_TRAIN and (FUSE_DEBLUR_TRAIN_AMP or dtype != torch.float16) and p.is_cuda and p.dtype == torch.float32
-            and model.n_feats % (8 if dtype == torch.float16 else 4) == 0
+            and model.n_feats % lanes(dtype) == 0
             and all(l.is_cuda and l.device == p.device and l.dtype == dtype and l.dim() == 4 and l.shape[1] in (3, 6)
                     and l.is_contiguous(memory_format=torch.channels_last) and l.numel() > 0 for l in levels))
 
@@ -419,12 +430,6 @@ def _forward_torch(model, levels):
         if s > 0:
             x = torch.cat((levels[s - 1][:, :3], model.conv_end_models[s](out[s])), 1)
     return out
-
-
-def _forward_amp_torch(model, levels):
-    """The reference's mixed-precision forward (models/deblur/train.py:97-99): the plain module under autocast."""
-    with torch.autocast(levels[0].device.type, dtype=torch.float16):
-        return _forward_torch(model, levels)
 
 
 def forward_amp_restated(model, levels):
@@ -475,26 +480,30 @@ def _forward_hip(model, levels):
     return out
 
 
+def choose_path(module, amp, hip_ok, hip_fn, torch_fn):
+    """The output of `hip_fn()` where `hip_ok`, else of `torch_fn()` -- with `amp`, the reference's mixed-precision forward
+    (models/deblur/train.py:97-99): the plain module under autocast.  `module.last_path` records which: "hip" / "torch", with
+    `amp` "hip-amp" / "torch-amp"."""
+    if hip_ok:
+        out = hip_fn()
+    elif amp:
+        with torch.autocast(next(module.parameters()).device.type, dtype=torch.float16):
+            out = torch_fn()
+    else:
+        out = torch_fn()
+    module.last_path = ("hip" if hip_ok else "torch") + ("-amp" if amp else "")
+    return out
+
+
 def msresnet_train_forward(model, input_levels):
     """`input_levels`: the levels minus 127.5, finest first, [B, 3, h, w] or [B, 6, h, w] with channels 0..2 holding the level
-    (`patch_levels`) -> the list of [B, 3, h, w] outputs of MSResNet before its `+ 127.5`, same order."""
+    (`patch_levels`) -> the list of [B, 3, h, w] outputs of MSResNet before its `+ 127.5`, same order.  Half levels into fp32
+    parameters (--amp): Half outputs; the caller takes the loss on their `.float()`."""
     if len(input_levels) != model.n_scales:
         raise ValueError("%d levels for a network of %d scales" % (len(input_levels), model.n_scales))
-    if _amp(model, input_levels):
-        # Half levels into fp32 parameters (--amp): Half outputs; the caller takes the loss on their `.float()`
-        if _hip_ok(model, input_levels, torch.float16):
-            out = _forward_hip(model, input_levels)
-            model.last_path = "hip-amp"
-        else:
-            out = _forward_amp_torch(model, input_levels)
-            model.last_path = "torch-amp"
-    elif _hip_ok(model, input_levels):
-        out = _forward_hip(model, input_levels)
-        model.last_path = "hip"
-    else:
-        out = _forward_torch(model, input_levels)
-        model.last_path = "torch"
-    return out
+    amp = _amp(model, input_levels)
+    return choose_path(model, amp, _hip_ok(model, input_levels, torch.float16 if amp else torch.float32),
+                       lambda: _forward_hip(model, input_levels), lambda: _forward_torch(model, input_levels))
 
 
 # ---- the loss --------------------------------------------------------------------------------------------------------------------
@@ -512,19 +521,23 @@ def l1_level_device(out, target, loss, gscale=1.0):
     return grad
 
 
-class _L1Pyramid(torch.autograd.Function):
-    """sum over levels of mean |out_s - target_s| as one node: dib_l1_pyramid_loss per level adds into one device scalar and stores
-    that level's gradient; the backward scales the stored gradients by the incoming one."""
+class _StoredGradSum(torch.autograd.Function):
+    """A sum of terms as one node: `term(x, item, loss)` adds the term of tensor x (with its target, or its label) into the 1-element
+    `loss` and returns d term / d x, which is stored; the backward scales the stored gradients by the incoming one."""
 
     @staticmethod
-    def forward(ctx, targets, *outs):
-        loss = torch.zeros(1, dtype=torch.float32, device=outs[0].device)
-        ctx.save_for_backward(*[l1_level_device(o.contiguous(memory_format=torch.channels_last), t, loss) for o, t in zip(outs, targets)])
+    def forward(ctx, term, items, *tensors):
+        loss = torch.zeros(1, dtype=tensors[0].dtype, device=tensors[0].device)
+        ctx.save_for_backward(*[term(x, item, loss) for x, item in zip(tensors, items)])
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, grad):
-        return (None,) + tuple(g * grad for g in ctx.saved_tensors)
+        return (None, None) + tuple(g * grad for g in ctx.saved_tensors)
+
+
+def stored_grad_sum(term, tensors, items):
+    return _StoredGradSum.apply(term, list(items), *tensors)
 
 
 def _l1_hip_ok(outputs, targets):
@@ -539,5 +552,6 @@ def pyramid_l1_loss(outputs, targets):
     if len(outputs) != len(targets):
         raise ValueError("%d outputs, %d targets" % (len(outputs), len(targets)))
     if _l1_hip_ok(outputs, targets):
-        return _L1Pyramid.apply(list(targets), *outputs)
+        # dib_l1_pyramid_loss per level: one device scalar for all levels
+        return stored_grad_sum(lambda o, t, loss: l1_level_device(o.contiguous(memory_format=torch.channels_last), t, loss), outputs, targets)
     return sum(F.l1_loss(o, t[:, :3]) for o, t in zip(outputs, targets))

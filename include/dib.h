@@ -865,7 +865,7 @@ int dib_deblur_patches_augment(const void *const *in_dev, int dtype, const int *
  * mask_dev NULL: no selection (any C >= 1), and grad_out_dev may be NULL too: the plain channel sum.  With a mask C % 4 == 0.
  * Tensors 16-byte aligned when C % 4 == 0, else 4-byte.  work_dev: dib_bias_grad_workspace_bytes(n_pix, C) bytes.
  * Two launches: per-slice partial sums into work_dev, then their sum in slice order; the order of every addition depends on
- * (n_pix, C) alone (csrc/dib_deblur_train.hip states it, with the depth of the tree for error bounds).  A NaN or inf gradient
+ * (n_pix, C) alone (csrc/dib_sliced_sum.h states it, with the depth of the tree for error bounds).  A NaN or inf gradient
  * reaches the sum of its own channel only.  DIB_EINVAL: n_pix or C < 1, n_pix * C > 2^40, null / misaligned pointer, a mask with
  * C % 4 != 0 or without grad_out_dev. */
 size_t dib_bias_grad_workspace_bytes(long long n_pix, int C);
@@ -889,7 +889,7 @@ int dib_bias_grad_f16_nhwc(const void *grad_in_dev, const unsigned char *mask_de
  * reference tree: a stated reading).  out_dev: the level's output, channels-last fp32 [n_pix][3]; target_dev: [n_pix][target_stride]
  * fp32 whose channels 0..2 are read (the layout dib_deblur_pyramid writes: stride 6, coarsest level 3).  With d = out - target:
  *     grad_dev[p][c] = sign(d) * k,  k = gscale / float(3 n_pix) (one fp32 division)      sign(+-0) = 0; a NaN d gives a NaN (torch.sign gives 0)
- *     *loss_dev     += (sum of |d|) / float(3 n_pix)                                     summed in a fixed order, as above
+ *     *loss_dev     += (sum of |d|) / float(3 n_pix)                                     summed in csrc/dib_sliced_sum.h's order
  * The caller zeroes *loss_dev before the first level.  work_dev: dib_l1_pyramid_loss_workspace_bytes(n_pix) bytes.  Two launches.
  * DIB_EINVAL: n_pix < 1 or > 2^38, target_stride < 3, null / misaligned (4 bytes) pointer. */
 size_t dib_l1_pyramid_loss_workspace_bytes(long long n_pix);
@@ -922,7 +922,7 @@ int dib_leaky_relu_mask_backward_f16(const void *grad_dev, const unsigned char *
  *     grad_dev[i] = (label 1: -1, label 0: +1) * (gscale / float(n)) * sigma(z)  sigma(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e)
  * A NaN logit gives a NaN at its own gradient element and a NaN loss, nothing else.  +-inf follows the formulas (z = +inf: term inf,
  * sigma 1; z = -inf: term 0, sigma 0), where torch's binary_cross_entropy_with_logits gives NaN.  Two launches; the sum is taken in
- * dib_l1_pyramid_loss's order, fixed by n alone (csrc/dib_deblur_adv.hip states it with its depth).  work_dev:
+ * dib_l1_pyramid_loss's order, fixed by n alone (csrc/dib_sliced_sum.h states it with its depth: the same kernels).  work_dev:
  * dib_adv_bce_loss_workspace_bytes(n) bytes.  DIB_EINVAL: n < 1 or > 2^40, real_label not 0 or 1, null / misaligned (4 bytes) pointer. */
 size_t dib_adv_bce_loss_workspace_bytes(long long n);
 int dib_adv_bce_loss(const float *logits_dev, long long n, int real_label, float gscale, float *grad_dev, float *loss_dev, void *work_dev,

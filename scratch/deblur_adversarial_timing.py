@@ -72,7 +72,7 @@ def steps(extra):
 
 FAMILIES = (("leaky_fwd_kernel<F32Lane, mask>", ("leaky_fwd_kernel", "F32Lane")), ("leaky_bwd_kernel<F32Lane>", ("leaky_bwd_kernel", "F32Lane")),
             ("leaky_fwd_kernel<F16Lane, mask>", ("leaky_fwd_kernel", "F16Lane")), ("leaky_bwd_kernel<F16Lane>", ("leaky_bwd_kernel", "F16Lane")),
-            ("adv_bce_partial_kernel + adv_bce_final_kernel (both precisions)", ("adv_bce_",)))
+            ("BCE loss: sliced_sum partial + final (both precisions)", ("BceTerm|adv_bce_",)))      # (a|b: the name before the kernels were shared)
 
 
 def report(directory):
@@ -85,7 +85,7 @@ def report(directory):
         raise SystemExit("no *kernel_trace.csv under %s" % directory)
     n = T.WARM + T.TRACED
     for title, keys in FAMILIES:
-        d = [t for t, name in rows if all(k in name for k in keys)]
+        d = [t for t, name in rows if all(any(a in name for a in k.split("|")) for k in keys)]
         if not d:
             print("%-66s no launch in the trace" % title)
             continue

@@ -139,7 +139,7 @@ def steps(extra):
     print("%d steps, %.2f ms per step under the tracer (warm-up included)" % (WARM + TRACED, dt * 1e3))
 
 
-FAMILIES = (("(a) patches_kernel", ("patches_kernel",)), ("(b) bias_grad_partial + final", ("bias_grad_",)), ("(c) l1_partial + final", ("l1_partial", "l1_final")),
+FAMILIES = (("(a) patches_kernel", ("patches_kernel",)), ("(b) bias_grad_partial + final", ("bias_grad_",)), ("(c) L1 loss: sliced_sum partial + final", ("L1Term", "l1_partial", "l1_final")),
             ("pyramid launches (deblur_level0 / deblur_down)", ("deblur_level0", "deblur_down")),
             ("bias_act forward epilogues", ("bias_act_kernel", "bias_act_f16_scalar")), ("the blur (blur_quad / blur_step / compaction)", ("blur_quad", "blur_step", "compact")))
 

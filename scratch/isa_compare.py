@@ -3,12 +3,15 @@ profiles/eltwise_unify_isa.txt).
 
     python scratch/isa_compare.py PARENT_TREE NEW_TREE dib_roi.hip > table.txt
     python scratch/isa_compare.py --pair epilogue PARENT_TREE NEW_TREE dib_eltwise.hip dib_eltwise_bf16.hip > table.txt
+    python scratch/isa_compare.py --pair sliced_sum PARENT_TREE NEW_TREE dib_deblur_train.hip dib_deblur_adv.hip > table.txt
 
 The named files of both trees' detectinblur_amd/csrc are compiled with csrc/Makefile's flags (--cuda-device-only -S,
 -Rpass-analysis=kernel-resource-usage).  A kernel's instruction stream is what is left of its function after dropping
 directives, comments and labels, with `.LBB<k>_<n>` renamed to `.LBB_<n>`.  Kernels are paired by demangled name without the
 parameter list (`roi_align_fwd_nhwc_sr_kernel<2>`); `--pair epilogue` pairs the trunk's epilogue family by stem, lane type and
-template flags instead, so `bias_act_vec4_kernel<1,1,0>` meets `bias_act_kernel<F32Lane,1,1,0>`.  CPU only: nothing is run.
+template flags instead, so `bias_act_vec4_kernel<1,1,0>` meets `bias_act_kernel<F32Lane,1,1,0>`; `--pair sliced_sum` pairs the
+trainer's scalar losses, so `l1_partial_kernel` meets `sliced_sum_partial_kernel<L1Term>` and `adv_bce_final_kernel` meets
+`sliced_sum_final_kernel<BceTerm>` (profiles/deblur_trainer_unify_isa.txt).  CPU only: nothing is run.
 """
 import argparse
 import collections
@@ -36,7 +39,15 @@ def pair_epilogue(demangled):
     return "%s<%s%s>" % (m.group(1), lane, "," + flags if flags else "")
 
 
-PAIRINGS = {"name": pair_by_name, "epilogue": pair_epilogue}
+def pair_sliced_sum(demangled):
+    name = pair_by_name(demangled)
+    m = re.match(r"(l1|adv_bce)_(partial|final)_kernel$", name)
+    if m:
+        return "sliced_sum_%s_kernel<%s>" % (m.group(2), {"l1": "L1Term", "adv_bce": "BceTerm"}[m.group(1)])
+    return name
+
+
+PAIRINGS = {"name": pair_by_name, "epilogue": pair_epilogue, "sliced_sum": pair_sliced_sum}
 
 
 def compile_tree(tree, files, pair, tmp):

@@ -205,6 +205,34 @@ def test_adv_bce_loss_against_float64_beside_torch(n, label, torchs_worst):
     assert torch.equal(_bits(ng[keep]), _bits(grad[keep]))
 
 
+@pytest.mark.parametrize("label", [0, 1])
+@pytest.mark.parametrize("n", [1, 257, 2049, 4099, 2048 * 1024, 2048 * 1024 + 5],
+                         ids=["1", "257", "2049-two-uneven-slices", "4099", "S1024-exactly", "capped-five-longer-slices"])
+def test_adv_bce_stated_order(n, label):
+    """The sum's order bit for bit: csrc/dib_sliced_sum.h's, as tests/test_deblur_train.py restates it in numpy float32 (`_walk`).  expf
+    and log1pf cannot be restated bit for bit, so the logits are chosen where the term does not depend on them: |x| >= 110 on the side
+    of the label at which z = |x|.  exp(-110) = 1.7e-48 lies below half the smallest fp32 denormal (7e-46), so e = expf(-|z|) is exactly
+    0 with or without denormal flushing, log1pf(0) is 0, the term is z itself and sigma is exactly 1: the loss is `_walk` over z, one
+    division by float32(n) and one addition onto a scalar that is not zero, and every gradient element is -+(float32(gscale) /
+    float32(n))."""
+    from detectinblur_amd.models import deblur_adversarial as DA
+    from tests.test_deblur_train import _F32, _real_draw, _walk, slice_begins
+    gscale, start = 0.75, 3.25
+    z = np.float32(110) + np.abs(_real_draw(np.random.RandomState(7 * n + label), n))
+    assert z.dtype == np.float32 and (z >= 110).all() and np.isfinite(z).all()
+    S = max(1, min(1024, -(-n // 2048)))
+    assert DA.adv_loss_depth(n) == -(-int(np.diff(slice_begins(n, S)).max()) // 256) + 8 + S - 1
+    want = np.float32(start) + _walk(n, S, 256, _F32(z)) / np.float32(n)
+    assert np.isfinite(want) and want.dtype == np.float32
+    k = np.float32(gscale) / np.float32(n)
+    x = torch.from_numpy(-z if label else z).cuda()
+    loss = torch.full((1,), start, device="cuda")
+    grad = DA.adv_bce_device(x, label, loss, gscale=gscale)
+    print("n", n, "label", label, "S", S, "loss %.9g, stated %.9g" % (float(loss), float(want)))
+    assert np.array_equal(loss.cpu().numpy().view(np.int32), np.array([want]).view(np.int32)), (float(loss), float(want))
+    assert np.array_equal(grad.cpu().numpy().view(np.int32), np.full(n, -k if label else k, dtype=np.float32).view(np.int32))
+
+
 def test_adv_bce_refusals_and_the_node(fused):
     from detectinblur_amd import _lib
     DA = fused

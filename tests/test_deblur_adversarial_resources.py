@@ -16,7 +16,8 @@ WAVES_PER_SIMD = 8
 # <L, MASK> of leaky_fwd_kernel and <L> of leaky_bwd_kernel as mangled
 LEAKY = ["leaky_fwd_kernelINS_7F32LaneELb1EE", "leaky_fwd_kernelINS_7F32LaneELb0EE", "leaky_fwd_kernelINS_7F16LaneELb1EE",
          "leaky_fwd_kernelINS_7F16LaneELb0EE", "leaky_bwd_kernelINS_7F32LaneEEE", "leaky_bwd_kernelINS_7F16LaneEEE"]
-LOSS = ["adv_bce_partial_kernel", "adv_bce_final_kernel"]
+# the loss's instantiations of csrc/dib_sliced_sum.h's two kernels as mangled
+LOSS = ["sliced_sum_partial_kernelINS_7BceTermEEE", "sliced_sum_final_kernelINS_7BceTermEEE"]
 
 
 @pytest.fixture(scope="module")

@@ -139,7 +139,7 @@ def test_depth_formulas_of_the_summation_trees():
 
 
 # ---- THE SUMMATION ORDER, restated in numpy float32 -----------------------------------------------------------------------------
-# Written from the header comment of csrc/dib_deblur_train.hip ("THE SUMMATION ORDER ... fixed by the shape alone"), not from the
+# Written from the header comment of csrc/dib_sliced_sum.h ("THE SUMMATION ORDER ... fixed by the shape alone"), not from the
 # kernel bodies: tests/test_deblur_train_geometry_gpu.py holds the kernels to these bit for bit.  Both reductions have one structure:
 # n items in memory order are cut into S slices of consecutive items; W lanes walk a slice, lane w adding items w, w + W, ... one
 # after the other; the W lane sums are added as a tree; the S slice sums are added one after the other from slice 0.  `_walk` states
