@@ -18,7 +18,7 @@ import time
 
 import torch
 
-from . import utils
+from . import blur_ops, quality, utils
 from .models import blur_functions, net_transforms
 
 
@@ -36,8 +36,6 @@ def _to_device(images_CPU, targets, blur_dicts, device, blurring, want_tables=Tr
     cuda = device.type == "cuda"
     if not cuda:
         return _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, False, blur_acc_mode)
-    from . import blur_ops
-    main = torch.cuda.current_stream(device)
     side = blur_ops.side_stream(device)
     with torch.cuda.stream(side):
         out = _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, True, blur_acc_mode)
@@ -106,7 +104,6 @@ def _stage(images_CPU, targets, blur_dicts, device, blurring, want_tables, cuda,
         active = [p for p, bd in zip(psfs_GPU, blur_dicts) if bd["blurring"]]
         if want_tables and cuda and active and len({tuple(p.shape) for p in active}) == 1 and active[0].dim() == 2 \
                 and active[0].shape[0] in (128, 256):
-            from . import blur_ops
             # fp16 images only (what the blur of this engine sees); the box growth reads the tap list, not the segments or the
             # vertical-run groups: boxes are the same in every mode
             _acc, vruns, large = blur_ops.resolve_acc_mode(blur_acc_mode, active[0].shape[0], torch.float16,
@@ -230,7 +227,6 @@ def _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, acc_mode=0):
         order = sorted(range(len(images_GPU)), key=lambda i: -int(blur_dicts[i]["psf_taps"]) if blur_dicts[i]["blurring"] else 1)
     except KeyError:
         pass
-    from . import blur_ops
     acc, _vruns, _large = blur_ops.resolve_acc_mode(acc_mode, tables.K, images_GPU[idx[0]].dtype, tables.large)
     tf.pending_blur = (index, tables, acc, order)
     return True
@@ -254,19 +250,40 @@ def _to_float(images_GPU, model, device):
     return [image.float().to(device) for image in images_GPU]
 
 
+def _grow_boxes(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables):
+    """--expand_target_boxes (reference engine.py:105, :317): the boxes grown by their image's PSF, from the staged tap tables"""
+    return utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
+
+
+class _Corruptions(object):
+    """What --gpu_blur's launch does to a batch besides blurring it (--add_noise / --noise_level, --add_block, --add_jpeg_artefacts) and
+    the arithmetic it runs in (--blur_acc_mode), unpacked once for `train_one_epoch` and `evaluate` alike (reference engine.py:56-62,
+    :248-254: the JPEG compressor is built only when asked for)."""
+
+    def __init__(self, device, add_noise, noise_level, add_block, add_jpeg_artifact, blur_acc_mode):
+        self.acc_mode = blur_ops.acc_mode_constant(blur_acc_mode)
+        # the corruptions take their random draws on the host, inside `blur_image_list`: such a batch is neither blurred ahead of its
+        # iteration nor left to the model's input transform
+        self.draws_on_host = bool(add_noise or add_block or add_jpeg_artifact)
+        jpeg_compressor = None
+        if add_jpeg_artifact:
+            from .models.jpeg import DiffJPEG
+            jpeg_compressor = DiffJPEG(height=100, width=100, differentiable=False, quality=10).to(device)
+        self.options = dict(add_noise=add_noise, noise_level=noise_level, add_block=add_block, add_jpeg_artifact=add_jpeg_artifact,
+                            jpeg_compressor=jpeg_compressor, acc_mode=self.acc_mode)
+
+    def blur(self, images_GPU, blur_dicts, psfs_GPU, tables):
+        blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, tables=tables, **self.options)
+
+
 def train_one_epoch(model, optimizer, data_loader, device, epoch=0, print_freq=200, writer=None, distributed_mode=False,
                     blur_train=False, early_stop=False, gpu_blur=False, expand_target_boxes=False,
                     use_custom_image_norm=False, add_noise=False, noise_level=0.001, add_block=False,
                     add_jpeg_artifact=False, blur_acc_mode="bitexact"):
     """`blur_acc_mode` (this repo, --blur_acc_mode): the arithmetic of the --gpu_blur launch, a key of blur_ops.ACC_MODES."""
-    from .blur_ops import acc_mode_constant
-    acc_mode = acc_mode_constant(blur_acc_mode)
+    corruptions = _Corruptions(device, add_noise, noise_level, add_block, add_jpeg_artifact, blur_acc_mode)
     if writer is None:
         print("Warning! No tensorboard logger.")
-    jpeg_compressor = None
-    if add_jpeg_artifact:                                                # reference :56-62
-        from .models.jpeg import DiffJPEG
-        jpeg_compressor = DiffJPEG(height=100, width=100, differentiable=False, quality=10).to(device)
     model.train()
     metric_logger = utils.MetricLogger(delimiter="  ")
     metric_logger.add_meter("lr", utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -296,15 +313,12 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch=0, print_freq=2
             blur_acc_mode=blur_acc_mode if gpu_blur else "bitexact")
         postponed = False
         if gpu_blur and blur_train:
-            if FUSE_BLUR_EPILOGUE and not (add_noise or add_block or add_jpeg_artifact):
-                postponed = _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, acc_mode)
+            if FUSE_BLUR_EPILOGUE and not corruptions.draws_on_host:
+                postponed = _postpone_blur(model, images_GPU, blur_dicts, psfs_GPU, tables, corruptions.acc_mode)
             if not postponed:
-                blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, add_noise=add_noise,
-                                               noise_level=noise_level, add_block=add_block,
-                                               add_jpeg_artifact=add_jpeg_artifact, jpeg_compressor=jpeg_compressor, acc_mode=acc_mode,
-                                               tables=tables)
+                corruptions.blur(images_GPU, blur_dicts, psfs_GPU, tables)
         if expand_target_boxes and blur_train:
-            targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
+            targets_GPU = _grow_boxes(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables)
         images_GPU = _to_float(images_GPU, model, device)
         norm_means, norm_stds = utils.get_norm_params(blur_dicts, use_custom_image_norm)
 
@@ -457,6 +471,175 @@ class EvaluationResult(object):
         return self._extra.keys()
 
 
+# ---- the parts of the evaluation loop (`evaluate`, below) ---------------------------------------------------------------------------
+
+class _FrontStage(object):
+    """What replaces image 0 of a batch in front of the detector -- `deblur_first` (reference :319-322: in a blurring pass and in the
+    vanilla pass, never in a pass that is neither) or `deconvolve_first` (a blurring pass only), never both -- and the
+    --restoration_metrics meter that compares the sharp, the blurred and the restored image (a pass that blurs on the device; None
+    otherwise: nothing allocated, nothing launched).  `prepare` calls `before_blur` and `after_blur` around the blur and the box growth;
+    everything either queues goes to the current stream and nothing is read back, so the look-ahead, the graphed trunk and the pictures
+    are untouched."""
+
+    def __init__(self, deblur_first, deblurer, deconvolve_first, deconvolver, blurring_images, vanilla_eval, restoration_metrics,
+                 restoration_quantize8, gpu_blur, device):
+        deblurring = bool(deblur_first) and (blurring_images or vanilla_eval)
+        if deblurring and deblurer is None:
+            raise ValueError("evaluate(deblur_first=True) needs a deblurer (models.deblur.Deblurer)")
+        deconvolving = bool(deconvolve_first) and blurring_images
+        if deconvolving and deconvolver is None:
+            raise ValueError("evaluate(deconvolve_first=True) needs a deconvolver (models.deconvolve.Deconvolver)")
+        if deconvolving and deblurring:
+            raise ValueError("evaluate: deblur_first and deconvolve_first both replace the image in front of the detector; choose one")
+        self.deblurer, self.deconvolver = deblurer if deblurring else None, deconvolver if deconvolving else None
+        self.replaces = deblurring or deconvolving
+        self.meter = None
+        if restoration_metrics and gpu_blur and blurring_images:
+            self.meter = quality.RestorationMeter(device, quantize8=restoration_quantize8,
+                                                  names=("blurred", "restored") if self.replaces else ("blurred",))
+
+    def before_blur(self, images_GPU, blur_dicts):
+        """--restoration_metrics: image 0 as it stands BEFORE the blur, one copy on this stream (None: this batch is not measured; an
+        image that is not blurred counts as skipped).  `blur_image_list` replaces the list ENTRY and today's blur paths write a fresh
+        tensor, so a reference would give the same figures; the copy (6.4 MB at full size) keeps the sharp image independent of how a
+        blur path treats its input."""
+        measured = self.meter is not None and bool(blur_dicts[0]["blurring"])
+        if self.meter is not None and not measured:
+            self.meter.skip()
+        return images_GPU[0].clone() if measured else None
+
+    def after_blur(self, images_GPU, blur_dicts, psfs_GPU, tables, sharp):
+        """the stage on images_GPU[0], in place of the list entry; then, with `sharp` from before_blur, the meter's two launches"""
+        blurred = images_GPU[0]      # a handle, no copy: a stage has to hand back a new tensor (checked below)
+        if self.deblurer is not None:
+            # the FIRST image only (batch size 1 in every driver).  On a GPU the image stays there: three HIP kernels and MIOpen's
+            # convolutions on the current stream, no synchronisation (models/deblur.py).  The result is fp32 (a Half deblurrer's: Half),
+            # as the reference hands it on: the estimator's batcher, the detector and the overlay all read this image, and all of them
+            # take either type (Half is what the blur hands them anyway).
+            images_GPU[0] = self.deblurer.deblur_(images_GPU[0])
+        if self.deconvolver is not None and blur_dicts[0]["blurring"]:
+            # the same place and the same image: 2 x iterations HIP launches on the current stream, no synchronisation.  The staged
+            # tables hold the blurring PSFs in batch order, so image 0's table is table 0; without staged tables (the CPU, mixed
+            # canvases) the stage compacts the PSF itself.  fp32 out, like the deblurrer's.
+            images_GPU[0] = self.deconvolver.deconvolve_(images_GPU[0], blur_dicts[0], psfs_GPU[0], tables, 0)
+        if sharp is not None:
+            restored = images_GPU[0] if self.replaces else None
+            if restored is not None and (restored is blurred or restored.data_ptr() == blurred.data_ptr()):
+                raise RuntimeError("evaluate(restoration_metrics=True): the stage handed back the tensor it was given; the blurred "
+                                   "image it would be compared with is gone (copy it before a stage that works in place)")
+            if restored is not None and restored.shape != sharp.shape:
+                raise RuntimeError("evaluate(restoration_metrics=True): the stage was given an image of %s and returned %s"
+                                   % (tuple(sharp.shape), tuple(restored.shape)))
+            self.meter.update(sharp, blurred, restored)      # Half from the blur, fp32 from the stages: the kernel takes the mix as it is
+
+    def result(self):
+        """behind the loop: {"restoration": the meter's figures}, printed as their table; {} without a meter"""
+        if self.meter is None:
+            return {}
+        figures = self.meter.result()                                    # one device read; a collective on every rank, like the evaluator's
+        print(quality.format_restoration(figures))
+        return {"restoration": figures}
+
+
+class _Scorer(object):
+    """The evaluator's updates.  `beside` (a GPU with graph inference asked for): the per-image COCO matching (host, ~2 ms) runs on ONE
+    worker thread, in submission order, while the main thread waits for the next image's detector: the ground-truth boxes of an image
+    are written before its update is submitted, and different images touch different annotations; the box-IoU kernel of the matching
+    runs on a stream of its own, never queued behind the detector.  `evaluator_time` then measures the hand-over."""
+
+    def __init__(self, coco_evaluator, device, beside):
+        self.coco_evaluator, self.pool, self.pending = coco_evaluator, None, []
+        if beside:
+            from concurrent.futures import ThreadPoolExecutor
+            self.pool = ThreadPoolExecutor(max_workers=1)
+            self.stream = torch.cuda.Stream(device=device)
+
+    def _score(self, res):
+        with torch.cuda.stream(self.stream):
+            self.coco_evaluator.update(res)
+
+    def update(self, res):
+        if self.pool is None:
+            self.coco_evaluator.update(res)                              # reference :388-392
+        else:
+            self.pending.append(self.pool.submit(self._score, res))      # scored while the GPU runs the next image
+
+    def shutdown(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+
+    def reraise(self):
+        for f in self.pending:
+            f.result()                                                   # re-raises anything the scoring thread hit
+
+
+class _Pipeline(object):
+    """The images on their way through a split detector (`launch_trunk` / `launch_heads` / `finish`, models/generalized_rcnn.py), in
+    image order: `trunk_running`, the one whose trunk has been launched, and `in_flight`, those whose heads have been; an entry is
+    (detector, handle, image ids, ground truth as xywh on the host, start time, picture).  `submit` is where the detections of every
+    image end up, whichever loop produced them."""
+
+    def __init__(self, scorer, pictures, metric_logger):
+        self.scorer, self.pictures, self.metric_logger = scorer, pictures, metric_logger
+        self.detections, self.gt_boxes = {}, {}
+        self.trunk_running, self.in_flight = None, []
+
+    def submit(self, ids, outputs, gt_xywh, started, picture=None):
+        """detections of one batch (CPU tensors) -> result tables + the evaluator (reference :376-392); `picture`: what `pictures.take` made"""
+        if picture is not None:
+            self.pictures.save(picture, outputs[0])                      # reference :382-383, inside model_time there too
+        model_time = time.time() - started
+        res = {}
+        for image_id, o, g in zip(ids, outputs, gt_xywh):
+            res[image_id] = o
+            self.detections[image_id] = o
+            self.gt_boxes[image_id] = g
+        evaluator_time = time.time()
+        self.scorer.update(res)
+        self.metric_logger.update(model_time=model_time, evaluator_time=time.time() - evaluator_time)
+
+    def finalize(self, ready):
+        """the first `ready` images in flight -- the caller has waited for their detections -- leave the pipeline through `submit`"""
+        for core, handle, ids, gt_xywh, started, picture in self.in_flight[:ready]:
+            self.submit(ids, core.finish(handle), gt_xywh, started, picture)
+        del self.in_flight[:ready]
+
+    def launch_heads(self):
+        """the RoI heads of the image whose trunk is running (the caller has waited for the trunk); the image joins `in_flight`"""
+        if self.trunk_running is not None:
+            if self.trunk_running[0].launch_heads(self.trunk_running[1]) is None:
+                raise RuntimeError("evaluate: the detector left the pipelined path between its trunk and its heads")
+            self.in_flight.append(self.trunk_running)
+            self.trunk_running = None
+
+    def flush(self):
+        """empties the pipeline, in image order: heads of the image whose trunk is running, then everything on its way"""
+        if self.trunk_running is not None:
+            torch.cuda.synchronize()
+            self.launch_heads()
+        if self.in_flight:
+            torch.cuda.synchronize()
+            self.finalize(len(self.in_flight))
+
+
+def _replace_ground_truth(coco_gt, targets_GPU):
+    """--expand_target_boxes: the expanded boxes replace the ground truth's, annotation k <- target box k (reference :325-342, index-wise:
+    where the target dropped a crowd / degenerate annotation the tail keeps its box).  Returns (annotations seen, faulty images)."""
+    total = faulty = 0
+    for target in targets_GPU:
+        boxes = utils.convert_to_xywh(target["boxes"]).cpu().numpy().tolist()
+        anns = coco_gt.imgToAnns[int(target["image_id"].item())]
+        for k, ann in enumerate(anns):
+            total += 1
+            if k < len(boxes):
+                ann["bbox"] = boxes[k]
+            elif k + 1 == len(anns):             # counted once per image, at its last annotation (reference :336-341)
+                faulty += 1
+            else:
+                print("Faulty " + str(len(anns) - k) + " times over.")
+    return total, faulty
+
+
 @torch.no_grad()
 def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None, vanilla_eval=False, blurring_images=False,
              gpu_blur=False, expand_target_boxes=False, deblur_first=False, deblurer=None, use_custom_image_norm=False,
@@ -487,33 +670,19 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     (overlay.py); `count` is the loop's index.  With more than one rank the files go to `<folder>/rank<r>/` (the reference lets the
     ranks overwrite each other).  On a GPU the picture is rendered by one HIP launch on the writer's stream and encoded on worker
     threads: no synchronisation is added to the loop."""
-    from .blur_ops import acc_mode_constant
     from .coco_eval import CocoEvaluator
     from .coco_utils import get_coco_api_from_dataset
-    acc_mode = acc_mode_constant(blur_acc_mode)
-    # reference :319: the stage runs in a blurring pass and in the vanilla pass, never in a pass that is neither
-    deblurring = bool(deblur_first) and (blurring_images or vanilla_eval)
-    if deblurring and deblurer is None:
-        raise ValueError("evaluate(deblur_first=True) needs a deblurer (models.deblur.Deblurer)")
-    deconvolving = bool(deconvolve_first) and blurring_images
-    if deconvolving and deconvolver is None:
-        raise ValueError("evaluate(deconvolve_first=True) needs a deconvolver (models.deconvolve.Deconvolver)")
-    if deconvolving and deblurring:
-        raise ValueError("evaluate: deblur_first and deconvolve_first both replace the image in front of the detector; choose one")
-    meter = None
-    if restoration_metrics and gpu_blur and blurring_images:
-        from .quality import RestorationMeter
-        meter = RestorationMeter(device, quantize8=restoration_quantize8,
-                                 names=("blurred", "restored") if (deblurring or deconvolving) else ("blurred",))
-    jpeg_compressor = None
-    if add_jpeg_artifact:                                                # reference :248-254
-        from .models.jpeg import DiffJPEG
-        jpeg_compressor = DiffJPEG(height=100, width=100, differentiable=False, quality=10).to(device)
+    from .overlay import EvaluationPictures
+    corruptions =_Corruptions(device, add_noise, noise_level, add_block, add_jpeg_artifact, blur_acc_mode)
+    front = _FrontStage(deblur_first, deblurer, deconvolve_first, deconvolver, blurring_images, vanilla_eval, restoration_metrics,
+                        restoration_quantize8, gpu_blur, device)
     n_threads = torch.get_num_threads()
     torch.set_num_threads(1)
     batcher = None
     # batch size 1 is launch-bound: the detectors' static trunk and the estimator replay as HIP graphs (graphs.py)
     graphed = device.type == "cuda" and not os.environ.get("DIB_NO_GRAPHS")
+    # the scoring thread goes by this FIRST value: --acclimate_norm may take the graphs away below, the matching still runs beside the loop
+    score_beside = graphed
     for m in (ensemble_models if use_ensemble else [model]):
         core = getattr(m, "module", m)
         if hasattr(core, "graph_inference"):
@@ -541,52 +710,13 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
     metric_logger = utils.MetricLogger(delimiter="  ")
     coco = get_coco_api_from_dataset(data_loader.dataset)                # reference :271-273
     coco_evaluator = CocoEvaluator(coco, ["bbox"], device=device if device.type == "cuda" else None)
-    detections, gt_boxes, routes = {}, {}, []
+    routes = []
     count = faulty_boxes = total_boxes = 0
-    # On a GPU the per-image COCO matching (host, ~2 ms) runs on ONE worker thread, in submission order, while the main
-    # thread waits for the next image's detector: the ground-truth boxes of an image are written before its update is
-    # submitted, and different images touch different annotations.  `evaluator_time` then measures the hand-over.
-    scorer, pending = None, []
-    if device.type == "cuda" and not os.environ.get("DIB_NO_GRAPHS"):
-        from concurrent.futures import ThreadPoolExecutor
-        scorer = ThreadPoolExecutor(max_workers=1)
-        score_stream = torch.cuda.Stream(device=device)
-
-        def score(res):           # the box-IoU kernel of the matching on its own stream: never queued behind the detector
-            with torch.cuda.stream(score_stream):
-                coco_evaluator.update(res)
-    png_writer = None
+    scorer = _Scorer(coco_evaluator, device, score_beside)
+    pictures = None
     try:
-        if image_output_folder is not None:
-            from . import overlay
-            folder = str(image_output_folder)
-            if utils.get_world_size() > 1:
-                folder = os.path.join(folder, "rank%d" % utils.get_rank())
-            png_writer = overlay.PngWriter(folder)
-
-        def picture_of(images_GPU, index):
-            """What `submit` needs to save image `index`'s picture: the first image of the batch as it stands now (the caller has just
-            synchronised: it is complete), an event that says so to the writer's stream, and the loop's index."""
-            if png_writer is None:
-                return None
-            image, complete = images_GPU[0], None
-            if image.is_cuda:
-                complete = torch.cuda.Event()
-                complete.record()
-            return image, complete, index
-
-        def save_picture(picture, output):
-            image, complete, index = picture
-            if not image.is_cuda:
-                overlay.save_png(png_writer.path(index), overlay.render_host(image, output["boxes"], output["labels"], output.get("scores")))
-                return
-            # render and copy on the writer's stream, behind the event; nothing here waits for the device (a full ring of
-            # pictures still being encoded does hold the loop: PngWriter.submit)
-            stream = png_writer.stream(image.device)
-            stream.wait_event(complete)
-            image.record_stream(stream)
-            with torch.cuda.stream(stream):
-                png_writer.submit(index, overlay.render_device([image], [output], stream=stream)[0])
+        pictures = EvaluationPictures(image_output_folder)
+        pipe = _Pipeline(scorer, pictures, metric_logger)
 
         # On a GPU the loop works one batch ahead (_StagedAhead): while the host waits for the detections of image i, image i + 1's
         # blur, box growth and blur-estimator pass are already queued, and image i + 2's upload runs on the side stream.  Only
@@ -594,42 +724,12 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
         def prepare(batch, staged):
             images_CPU, targets_CPU, blur_dicts = batch
             images_GPU, targets_GPU, psfs_GPU, thetas, l1, l2, tables = staged
-            # --restoration_metrics: image 0 as it stands BEFORE the blur (one copy on this stream), the blurred image the detector or
-            # the stage gets, and what the stage makes of it; quality.RestorationMeter queues two launches behind the stage on this
-            # stream and reads nothing, so the look-ahead, the graphed trunk and the pictures are untouched.  `blur_image_list` replaces
-            # the list ENTRY and today's blur paths write a fresh tensor, so a reference would give the same figures; the copy (6.4 MB
-            # at full size) keeps the sharp image independent of how a blur path treats its input
-            measured = meter is not None and gpu_blur and blurring_images and bool(blur_dicts[0]["blurring"])
-            if meter is not None and not measured:
-                meter.skip()
-            sharp = images_GPU[0].clone() if measured else None
+            sharp = front.before_blur(images_GPU, blur_dicts)
             if gpu_blur and blurring_images:
-                blur_functions.blur_image_list(images_GPU, blur_dicts, psfs_GPU=psfs_GPU, add_noise=add_noise, noise_level=noise_level,
-                                               add_block=add_block, add_jpeg_artifact=add_jpeg_artifact,
-                                               jpeg_compressor=jpeg_compressor, acc_mode=acc_mode, tables=tables)
+                corruptions.blur(images_GPU, blur_dicts, psfs_GPU, tables)
             if expand_target_boxes and blurring_images:
-                targets_GPU = utils.expand_targets(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables=_tables_128(tables))
-            blurred = images_GPU[0]      # a handle, no copy: a stage has to hand back a new tensor (checked below)
-            if deblurring:
-                # reference :319-322, the FIRST image only (batch size 1 in every driver).  On a GPU the image stays there: three HIP
-                # kernels and MIOpen's convolutions on the current stream, no synchronisation (models/deblur.py).  The result is
-                # fp32 (a Half deblurrer's: Half), as the reference hands it on: the estimator's batcher, the detector and the
-                # overlay all read this image, and all of them take either type (Half is what the blur hands them anyway).
-                images_GPU[0] = deblurer.deblur_(images_GPU[0])
-            if deconvolving and blur_dicts[0]["blurring"]:
-                # the same place and the same image: 2 x iterations HIP launches on the current stream, no synchronisation.  The staged
-                # tables hold the blurring PSFs in batch order, so image 0's table is table 0; without staged tables (the CPU, mixed
-                # canvases) the stage compacts the PSF itself.  fp32 out, like the deblurrer's.
-                images_GPU[0] = deconvolver.deconvolve_(images_GPU[0], blur_dicts[0], psfs_GPU[0], tables, 0)
-            if measured:
-                restored = images_GPU[0] if (deblurring or deconvolving) else None
-                if restored is not None and (restored is blurred or restored.data_ptr() == blurred.data_ptr()):
-                    raise RuntimeError("evaluate(restoration_metrics=True): the stage handed back the tensor it was given; the blurred "
-                                       "image it would be compared with is gone (copy it before a stage that works in place)")
-                if restored is not None and restored.shape != sharp.shape:
-                    raise RuntimeError("evaluate(restoration_metrics=True): the stage was given an image of %s and returned %s"
-                                       % (tuple(sharp.shape), tuple(restored.shape)))
-                meter.update(sharp, blurred, restored)      # Half from the blur, fp32 from the stages: the kernel takes the mix as it is
+                targets_GPU = _grow_boxes(targets_GPU, blur_dicts, psfs_GPU, images_GPU, tables)
+            front.after_blur(images_GPU, blur_dicts, psfs_GPU, tables, sharp)
             images_GPU = _to_float(images_GPU, ensemble_models[0] if use_ensemble else model, device)
             est = None
             if use_ensemble and blur_estimator is not None:                  # reference :354-366 (the routing itself: below)
@@ -637,70 +737,20 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 est = _estimate(blur_estimator, batched.tensors, graphed)
             return images_GPU, targets_GPU, blur_dicts, thetas, l1, l2, est
 
-        def submit(ids, outputs, gt_xywh, started, picture=None):
-            """detections of one batch (CPU tensors) -> result tables + the evaluator (reference :376-392); `picture`: picture_of()"""
-            if picture is not None:
-                save_picture(picture, outputs[0])                            # reference :382-383, inside model_time there too
-            model_time = time.time() - started
-            res = {}
-            for image_id, o, g in zip(ids, outputs, gt_xywh):
-                res[image_id] = o
-                detections[image_id] = o
-                gt_boxes[image_id] = g
-            evaluator_time = time.time()
-            if scorer is None:
-                coco_evaluator.update(res)                                   # reference :388-392
-            else:
-                pending.append(scorer.submit(score, res))                    # scored while the GPU runs the next image
-            metric_logger.update(model_time=model_time, evaluator_time=time.time() - evaluator_time)
-
-        def finalize(entry):
-            core_, handle_, ids_, gt_, started_, picture_ = entry
-            submit(ids_, core_.finish(handle_), gt_, started_, picture_)
-
         # models whose internal warp is on need thetas / lambdas in forward: they stay on the plain loop
         pipelined = (graphed and not os.environ.get("DIB_NO_PIPELINE")
                      and not any(getattr(getattr(m, "module", m), "warp_internally", False) and blurring_images
                                  for m in (ensemble_models if use_ensemble else [model])))
-        trunk_running, in_flight = None, []
-
-        def flush():
-            """empties the pipeline, in image order: heads of the image whose trunk is running, then everything on its way"""
-            nonlocal trunk_running, in_flight
-            if trunk_running is not None:
-                torch.cuda.synchronize()
-                if trunk_running[0].launch_heads(trunk_running[1]) is None:
-                    raise RuntimeError("evaluate: the detector left the pipelined path between its trunk and its heads")
-                in_flight.append(trunk_running)
-                trunk_running = None
-            if in_flight:
-                torch.cuda.synchronize()
-                for entry in in_flight:
-                    finalize(entry)
-                in_flight = []
-
         ahead = _StagedAhead(metric_logger.log_every(data_loader, 100, "Test:"), device, blurring_images, gpu_blur or expand_target_boxes,
-                             prepare, may_prepare=not (add_noise or add_block or add_jpeg_artifact),
-                             blur_acc_mode=blur_acc_mode if gpu_blur else "bitexact")
+                             prepare, may_prepare=not corruptions.draws_on_host, blur_acc_mode=blur_acc_mode if gpu_blur else "bitexact")
         for _, (images_GPU, targets_GPU, blur_dicts, thetas, l1, l2, est) in ahead:
             if device.type == "cuda":
                 torch.cuda.synchronize()
             model_time = time.time()
-            picture = picture_of(images_GPU, count)
+            picture = pictures.take(images_GPU, count)
             if expand_target_boxes and blurring_images:
-                # the expanded boxes replace the ground truth's, annotation k <- target box k (reference :325-342,
-                # index-wise: where the target dropped a crowd / degenerate annotation the tail keeps its box)
-                for target in targets_GPU:
-                    boxes = utils.convert_to_xywh(target["boxes"]).cpu().numpy().tolist()
-                    anns = coco_evaluator.coco_gt.imgToAnns[int(target["image_id"].item())]
-                    for k, ann in enumerate(anns):
-                        total_boxes += 1
-                        if k < len(boxes):
-                            ann["bbox"] = boxes[k]
-                        elif k + 1 == len(anns):             # counted once per image, at its last annotation (reference :336-341)
-                            faulty_boxes += 1
-                        else:
-                            print("Faulty " + str(len(anns) - k) + " times over.")
+                total, faulty = _replace_ground_truth(coco_evaluator.coco_gt, targets_GPU)
+                total_boxes, faulty_boxes = total_boxes + total, faulty_boxes + faulty
             norm_means, norm_stds = utils.get_norm_params(blur_dicts, use_custom_image_norm)
 
             if use_ensemble:                                                 # reference :354-366
@@ -716,7 +766,7 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
             ids = [int(t["image_id"]) if "image_id" in t else count for t in targets_GPU]
             handle = None
             if not (pipelined and hasattr(core, "launch_trunk")):
-                flush()                                                      # a detector without the split forward pass: images stay in order
+                pipe.flush()                                                 # a detector without the split forward pass: images stay in order
             else:
                 # Pipelined (GPU, graph inference): the queue is empty here (the synchronisation above).  Queue, in this order and
                 # without waiting for any of it: the RoI heads + detections of the PREVIOUS image (its trunk has finished: reading
@@ -724,22 +774,16 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 # estimator pass and the upload of the one after; then turn the detections that were copied before the
                 # synchronisation into evaluator updates while the GPU works.  Same tensors through the same kernels as the
                 # plain loop below (tests/test_full_size_gpu.py compares the two).
-                ready, in_flight = in_flight, []
+                ready = len(pipe.in_flight)                                  # their detections were copied before the synchronisation
                 gt_host = [utils.convert_to_xywh(t["boxes"]).cpu() for t in targets_GPU]      # before anything is queued: no wait
-                if trunk_running is not None:
-                    if trunk_running[0].launch_heads(trunk_running[1]) is None:
-                        raise RuntimeError("evaluate: the detector left the pipelined path between its trunk and its heads")
-                    in_flight.append(trunk_running)
-                    trunk_running = None
+                pipe.launch_heads()
                 handle = core.launch_trunk(images_GPU, killWarp=not blurring_images, newMeans=norm_means, newSTDs=norm_stds)
                 if handle is not None:
-                    trunk_running = (core, handle, ids, gt_host, model_time, picture)
+                    pipe.trunk_running = (core, handle, ids, gt_host, model_time, picture)
                     ahead.advance(more=more)
-                    for entry in ready:
-                        finalize(entry)
+                    pipe.finalize(ready)
                 else:                                                        # this detector does not take the path: drain, then as below
-                    in_flight = ready + in_flight
-                    flush()
+                    pipe.flush()
             if handle is None:
                 # the look-ahead step runs right after the detector's trunk has been launched (models/generalized_rcnn.py calls
                 # the hook between the graph replay and its first wait); a model without that hook gets it before the call
@@ -755,30 +799,24 @@ def evaluate(model, data_loader, device, distributed_mode=False, early_stop=None
                 if hooked and core.__dict__.pop("_after_trunk_launch", None) is not None:
                     ahead.advance(more=more)                                  # the forward pass took a path without the hook
                 outputs = [{k: v.to("cpu") for k, v in t.items()} for t in outputs]
-                submit(ids, outputs, [utils.convert_to_xywh(t["boxes"]).cpu() for t in targets_GPU], model_time, picture)
+                pipe.submit(ids, outputs, [utils.convert_to_xywh(t["boxes"]).cpu() for t in targets_GPU], model_time, picture)
             count += 1
             if early_stop is not None and count > early_stop:
                 break
-        flush()                                                              # the pipeline's tail
+        pipe.flush()                                                         # the pipeline's tail
     finally:                                                             # also on an error in the loop: no stray thread, thread count restored
-        if scorer is not None:
-            scorer.shutdown(wait=True)
+        scorer.shutdown()
         torch.set_num_threads(n_threads)
-        if png_writer is not None:
-            png_writer.close()                                           # drains the encoders; re-raises the first error one of them hit
-    for f in pending:
-        f.result()                                                       # re-raises anything the scoring thread hit
+        if pictures is not None:
+            pictures.close()                                             # drains the encoders; re-raises the first error one of them hit
+    scorer.reraise()
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
-    extra = {}
-    if meter is not None:
-        from .quality import format_restoration
-        extra["restoration"] = meter.result()                            # one device read; a collective on every rank, like the evaluator's
-        print(format_restoration(extra["restoration"]))
+    extra = front.result()
     print("Number of Faulty boxes: " + str(faulty_boxes) + " Total number of boxes: " + str(total_boxes))
     coco_evaluator.synchronize_between_processes()                       # a collective on every rank, shards empty or not
     coco_evaluator.accumulate()
     stats = coco_evaluator.summarize() if utils.is_main_process() else coco_evaluator.coco_eval["bbox"].summarize()
     has_gt = len(coco_evaluator.coco_gt.dataset.get("annotations", [])) > 0
-    return EvaluationResult(coco_evaluator, detections=detections, targets=gt_boxes, routes=routes, meters=metric_logger,
+    return EvaluationResult(coco_evaluator, detections=pipe.detections, targets=pipe.gt_boxes, routes=routes, meters=metric_logger,
                             coco_stats=stats if has_gt else None, **extra)

@@ -266,3 +266,47 @@ class PngWriter(object):
         self._slots = [None] * self.depth
         for f in futures:
             f.result()
+
+
+class EvaluationPictures(object):
+    """The pictures of one pass of engine.evaluate (`image_output_folder`; None: no picture, no writer): a PngWriter on the folder
+    -- with more than one rank on `<folder>/rank<r>/` (the reference lets the ranks overwrite each other) -- fed by the loop in two
+    steps, `take` where the image is complete and `save` where its detections have arrived."""
+
+    def __init__(self, image_output_folder):
+        from . import utils
+        self.writer = None
+        if image_output_folder is not None:
+            folder = str(image_output_folder)
+            if utils.get_world_size() > 1:
+                folder = os.path.join(folder, "rank%d" % utils.get_rank())
+            self.writer = PngWriter(folder)
+
+    def take(self, images, index):
+        """What `save` needs for image `index`'s picture: the first image of the batch as it stands now (the caller has just
+        synchronised: it is complete), an event that says so to the writer's stream, and the loop's index."""
+        if self.writer is None:
+            return None
+        image, complete = images[0], None
+        if image.is_cuda:
+            complete = torch.cuda.Event()
+            complete.record()
+        return image, complete, index
+
+    def save(self, picture, output):
+        image, complete, index = picture
+        if not image.is_cuda:
+            save_png(self.writer.path(index), render_host(image, output["boxes"], output["labels"], output.get("scores")))
+            return
+        # render and copy on the writer's stream, behind the event; nothing here waits for the device (a full ring of
+        # pictures still being encoded does hold the loop: PngWriter.submit)
+        stream = self.writer.stream(image.device)
+        stream.wait_event(complete)
+        image.record_stream(stream)
+        with torch.cuda.stream(stream):
+            self.writer.submit(index, render_device([image], [output], stream=stream)[0])
+
+    def close(self):
+        """`evaluate`'s `finally`: drains the encoders; re-raises the first error one of them hit"""
+        if self.writer is not None:
+            self.writer.close()
